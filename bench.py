@@ -16,9 +16,18 @@ overflows the MTU).  ``value`` is the cluster's exchanges / the slowest rank's t
 
 Prints ONE JSON line (rank 0) with the roofline of the dominant kernel (k_pass1; each phase is k_pass1,
 then k_lite -- whole deltas sized from the owners' version logs and applied -- then the exact packer for
-the rest; every kernel HIP-event timed on the library's stream, gs_kernel_times), the CPU baseline (the C oracle on 16 host threads and on one, timed
-on a bounded sample of exchanges whose rows are copied from the device state after the timed rounds,
-checked bit-exact against the device first) and 3 rounds scheduled by the device's own peer selection.
+the rest; every kernel HIP-event timed on the library's stream during the timed steps, gs_kernel_times).
+
+A plain run sets up (the settle rounds included), warms up, times ``--steps`` rounds, writes its outputs if
+``--dump-outputs DIR`` is given and prints the line.  ``--full`` adds every measurement and check that takes
+runs of its own: the CPU baseline (the C oracle on 16 host threads and on one, timed on a bounded sample of
+exchanges whose rows are copied from the device state after the timed rounds, checked bit-exact against the
+device first), 3 rounds scheduled by the device's own peer selection, the measured streaming-copy ceiling of
+the roofline, the exactness horizon and the count of inexact views, the parity check of a sliced run and the
+config-4 leg.  Without ``--full`` those fields of the line are null (``inexact_views`` is absent).
+
+``--dump-outputs DIR`` writes, after the timed steps, the state their last round left behind as a caller
+reads it back (``GossipSim.export_rows``) to ``DIR/<name>.npy``: see ``dump_outputs``.
 """
 
 from __future__ import annotations
@@ -337,7 +346,7 @@ def pass1_kernel(wide_views: bool) -> str:
 
 
 def roofline(sims, local_c, exch, kt, elapsed, torch, dev, rank, group, workload, p1name="k_pass1",
-             steps: int = 1) -> dict:
+             steps: int = 1, copy: bool = True) -> dict:
     """Roofline of the dominant kernel (by summed time; HBM-bound integer/byte work, no MFMA) plus the
     same figures for the other kernels of the round.
 
@@ -384,7 +393,8 @@ def roofline(sims, local_c, exch, kt, elapsed, torch, dev, rank, group, workload
         per[kind] = ent
     dom = max(per, key=lambda k: kt[k][0])
     d = per[dom]
-    copy_gbs = copy_ceiling(torch, dev, sims[0].stream) if rank == 0 else None
+    # the measured ceiling is a run of its own (2 GiB copies): --full only
+    copy_gbs = copy_ceiling(torch, dev, sims[0].stream) if (rank == 0 and copy) else None
     launches = kt["pass1"][1] or 1
     survey = (exch * 32 * ncols + packb) / launches
     # the whole step: every phase kernel's and k_liveness' in-kernel algorithmic bytes of the timed rounds over
@@ -579,6 +589,40 @@ def mark(sim, which: int) -> None:
     assert rc == 0, rc
 
 
+DUMP_ROWS, DUMP_COLS, DUMP_SEED = 8, 2048, 20240607
+# exact in binary32 (small counts, flags, ticks / 64 below 2^24); the others (value ids from 2^24, ticks) in binary64
+DUMP_F32 = ("hb", "mv", "gc", "pos", "fd_len", "fd_sum", "live", "kv_version", "kv_status")
+
+
+def dump_outputs(sim, counters: dict, out_dir: str) -> dict:
+    """``--dump-outputs``: what the timed rounds computed, as a caller reads it back after the last of them.
+
+    ``GossipSim.export_rows`` (the oracle's export format, times in ticks) of DUMP_ROWS observer rows drawn
+    with a fixed seed: the per-view arrays (hb, mv, gc, pos, fd_last, fd_len, fd_sum, live, tod) over every
+    owner column of the slice, the per-key arrays (kv_version, kv_status, kv_value_id, kv_ts) over DUMP_COLS
+    owner columns drawn with the same seed; ``sample_rows`` / ``sample_cols`` hold the drawn indices and
+    ``counters`` the device counters of the timed steps in ``_lib.COUNTER_FIELDS`` order (sums over every
+    exchange of every row: integer, order-independent).  Each array goes to ``out_dir/<name>.npy`` as float32
+    where that is exact for its values, else float64; about 30 MB at 65,536 nodes.  Returns {name: shape}."""
+    from aiocluster_amd import _lib
+
+    rng = np.random.default_rng(DUMP_SEED)
+    rows = np.sort(rng.choice(sim.n, size=min(DUMP_ROWS, sim.n), replace=False))
+    cols = np.sort(rng.choice(sim.ncol, size=min(DUMP_COLS, sim.ncol), replace=False))
+    ex = sim.export_rows(rows)
+    out = {"sample_rows": rows.astype(np.float64), "sample_cols": cols.astype(np.float64),
+           "counters": np.asarray([counters[f] for f in _lib.COUNTER_FIELDS], dtype=np.float64)}
+    for name, a in ex.items():
+        a = a[:, cols] if a.ndim == 3 else a
+        out[name] = np.ascontiguousarray(a, dtype=np.float32 if name in DUMP_F32 else np.float64)
+    total = sum(a.nbytes for a in out.values())
+    assert total <= 64 << 20, total
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in out.items()}
+
+
 def launch_ranks(n: int) -> int:
     """``--gpus N`` without a torch.distributed launcher: start N ranks (one per GPU) with
     torch.distributed.run as a child process -- before this process touches the GPU -- and return its
@@ -604,6 +648,13 @@ def main():
     ap.add_argument("--keys", type=int, default=16)
     ap.add_argument("--fanout", type=int, default=3)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run what takes runs of its own: the CPU baseline and its "
+                         "parity check, the peer-selected rounds, the measured copy ceiling, the exactness horizon, "
+                         "a sliced run's parity check and the config-4 leg (without it those fields are null)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the state their last round left, read back as a caller "
+                         "would (a fixed, seeded sample of observer rows; see dump_outputs), to DIR/<name>.npy")
     ap.add_argument("--settle", type=int, default=20,
                     help="untimed rounds run as part of setup, before the warmup: the warm start has every view "
                          "equal to its owner, and the heartbeat / version lags reach their steady-state spread "
@@ -612,30 +663,30 @@ def main():
     ap.add_argument("--cpu-seconds", type=float, default=10.0)
     ap.add_argument("--cpu-threads", type=int, default=min(16, len(os.sched_getaffinity(0))),
                     help="host threads for the CPU baseline (the GPU box's CPU share is 16)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     ap.add_argument("--slices", type=int, default=1, help="owner-column slices in this process (1-GPU rehearsal)")
     ap.add_argument("--mtu", type=int, default=65507)
     ap.add_argument("--parity-sample", type=int, default=16,
-                    help="sliced runs (--gpus N > 1, --slices G): after the timed rounds, check this many exchanges "
+                    help="--full, sliced runs (--gpus N > 1, --slices G): after the timed rounds, check this many exchanges "
                          "of the next round's first phase against the C oracle on whole-cluster rows joined from "
                          "every slice (0 = skip)")
     ap.add_argument("--peer-select", action="store_true",
                     help="schedule each round with the device's select_nodes_for_gossip (gs_select_peers) and "
                          "Luby phases (gs_schedule_phases) instead of the workload's permutation schedule")
     ap.add_argument("--peer-select-steps", type=int, default=3,
-                    help="after the headline: time this many more rounds scheduled by the device's "
+                    help="--full, after the headline: time this many more rounds scheduled by the device's "
                          "select_nodes_for_gossip (gs_select_peers) + Luby phases (gs_schedule_phases), reported "
                          "as the line's peer_select object (0 = skip)")
     ap.add_argument("--rehearse-slices", type=int, default=0,
                     help="hold only slice 0 of G owner-column slices (one GPU's share of a G-GPU run; timing only "
                          "unless the mtu cannot bind)")
     ap.add_argument("--config4-steps", type=int, default=3,
-                    help="with --gpus 8: after the headline, time this many rounds of BASELINE config 4 (262,144 "
+                    help="--full with --gpus 8: after the headline, time this many rounds of BASELINE config 4 (262,144 "
                          "nodes, one owner-column slice of 32,768 columns per GPU, version-only views, mtu 2^30), "
                          "reported as the line's config4 object (0 = skip)")
     ap.add_argument("--config4-settle", type=int, default=3, help="untimed config-4 rounds before its warmup")
     ap.add_argument("--config4", action="store_true",
-                    help="on one GPU: also run the config-4 leg as slice 0 of 8 held alone (one GPU's share)")
+                    help="--full on one GPU: also run the config-4 leg as slice 0 of 8 held alone (one GPU's share)")
     ap.add_argument("--native-comm", action="store_true",
                     help="--gpus N: the library drives each sliced phase over its own RCCL communicator "
                          "(gs_comm_init + gs_run_phase) instead of aiocluster_amd/shard.py over torch.distributed; "
@@ -719,8 +770,10 @@ def main():
         sims = [GossipSim(ids, key_names(K), cfg, **kw)]
     sim = sims[0]
     R0 = args.settle + args.warmup  # first timed round
-    ps_steps = args.peer_select_steps if (group is None and not args.peer_select) else 0
-    plans = driver.prepare(spec, R0 + args.steps + 1 + (1 + ps_steps if ps_steps else 0), torch, dev)
+    ps_steps = args.peer_select_steps if (args.full and group is None and not args.peer_select) else 0
+    # (plans are generated round by round from the seed: the legs of --full only append rounds after the timed ones)
+    plans = driver.prepare(spec, R0 + args.steps + (1 + (1 + ps_steps if ps_steps else 0) if args.full else 0),
+                           torch, dev)
     sel = None
     if args.peer_select:
         from aiocluster_amd.peers import PeerSelector
@@ -758,7 +811,8 @@ def main():
         dist.barrier()
     elapsed = time.perf_counter() - t0
     local_c = [s_.check() for s_ in sims]
-    inexact = sum(s_.inexact_views() for s_ in sims)  # views with holes (HELD kept), GS_MV_INEXACT
+    # views with holes (HELD kept), GS_MV_INEXACT: a scan of the whole MV region
+    inexact = sum(s_.inexact_views() for s_ in sims) if args.full else None
     c = group.comm.sum_counters(local_c) if group is not None else local_c[0]
     exch = sum(plans[r]["exchanges"] for r in range(R0, R0 + args.steps))
     unscheduled = sum(plans[r].get("unscheduled", 0) for r in range(R0, R0 + args.steps))
@@ -769,14 +823,19 @@ def main():
     # a sliced cluster: every rank runs the same exchanges on its columns -> count them once
     exch_total, elapsed_max = aggregate(exch if (group is None or rank == 0) else 0, elapsed, dist, dev)
     roof = roofline(sims[:1], local_c[:1], exch, kt, elapsed, torch, dev, rank, group, workload,
-                    pass1_kernel(args.wide_views), steps=args.steps)
+                    pass1_kernel(args.wide_views), steps=args.steps, copy=args.full)
+    dumped = None
+    if args.dump_outputs and rank == 0:  # (a sliced run: rank 0's first slice, its own owner columns)
+        t_dump = time.perf_counter()
+        dumped = dump_outputs(sims[0], local_c[0], args.dump_outputs)
+        log(f"outputs written to {args.dump_outputs} in {time.perf_counter() - t_dump:.1f}s")
     cpu = None
-    if rank == 0 and group is None and not args.no_cpu_baseline:
+    if args.full and rank == 0 and group is None and not args.no_cpu_baseline:
         rd = plans[R0 + args.steps]
         driver.begin(sims, rd)
         cpu = cpu_baseline(sim, cfg, rd, args.cpu_sample, args.cpu_seconds, args.cpu_threads)
     par = None
-    if group is not None and args.rehearse_slices <= 1 and args.parity_sample:
+    if args.full and group is not None and args.rehearse_slices <= 1 and args.parity_sample:
         # the sliced run's own parity evidence: the round after the timed ones, phase 0's
         # first exchanges, whole-cluster rows joined from every slice vs the C oracle
         rd = plans[R0 + args.steps]
@@ -793,10 +852,10 @@ def main():
         ps["exact"] = not errs
     rounds_run = (R0 + args.steps + (1 if (cpu is not None or par is not None) else 0)
                   + (ps_steps + 1 if ps is not None else 0))
-    horizon = sims[0].horizon(rounds=rounds_run)
+    horizon = sims[0].horizon(rounds=rounds_run) if args.full else None  # (scans the whole FD region)
     sliced = group is not None  # (the config-4 leg below releases the headline's handles first)
     c4 = None
-    if args.config4_steps and (world == C4_GPUS or args.config4):
+    if args.full and args.config4_steps and (world == C4_GPUS or args.config4):
         for s_ in sims:
             s_.close()
         del sims, sim, group
@@ -845,12 +904,15 @@ def main():
             **({"parity_check": par} if par is not None else {}),
             "peer_select": ps,
             **({"ABLATION_RESULTS_INVALID": os.environ["GS_ABLATE"]} if os.environ.get("GS_ABLATE") else {}),
-            "counters": {**{k: v for k, v in c.items() if not k.startswith("err_")}, "inexact_views": inexact},
+            "counters": {**{k: v for k, v in c.items() if not k.startswith("err_")},
+                         **({"inexact_views": inexact} if inexact is not None else {})},
             # headroom to the exact layout's two bounds: err_fd_overflow at a window count of W (compact
             # windows), err_hist_full at hist_cap - 1 writes of one (owner, key); each projected in rounds at
             # the growth rate of this run; fd_saturated (sampled rings' inexact compact rows) raises in check()
             "exactness": horizon,
             "config4": c4,
+            "full": args.full,
+            **({"outputs": {"dir": args.dump_outputs, "arrays": dumped}} if dumped is not None else {}),
         }
         print(json.dumps(line), flush=True)
     if dist is not None:

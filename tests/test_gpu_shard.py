@@ -379,7 +379,7 @@ def test_sliced_parity_check_reports_a_corrupted_slice(monkeypatch):
 
 
 def test_bench_two_ranks_gloo_rehearsal_reports_parity_per_slice():
-    """`GS_BENCH_BACKEND=gloo python bench.py --gpus 2` (both ranks on this GPU, gathers through host memory): the
+    """`GS_BENCH_BACKEND=gloo python bench.py --full --gpus 2` (both ranks on this GPU, gathers through host memory): the
     multi-rank bench's rank plumbing end to end, with its own parity evidence -- the line carries parity_check,
     bit-exact for each slice."""
     import json
@@ -389,7 +389,7 @@ def test_bench_two_ranks_gloo_rehearsal_reports_parity_per_slice():
 
     repo = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, GS_BENCH_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
-    cmd = [sys.executable, os.path.join(repo, "bench.py"), "--gpus", "2", "--nodes", "4096", "--steps", "2",
+    cmd = [sys.executable, os.path.join(repo, "bench.py"), "--full", "--gpus", "2", "--nodes", "4096", "--steps", "2",
            "--warmup", "1", "--settle", "4", "--mtu", "3000", "--parity-sample", "32"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600, cwd=repo)
     assert r.returncode == 0, r.stderr[-4000:]

@@ -91,3 +91,55 @@ def test_multi_rank_aggregation_gloo():
     for p in procs:
         p.join(60)
     assert [o[1:] for o in out] == [(3000.0, 3.0), (3000.0, 3.0)]
+
+
+class _ExportOnly:
+    """The part of GossipSim that bench.dump_outputs reads: n, ncol, export_rows (the oracle's export format)."""
+
+    def __init__(self, n, k):
+        self.n = self.ncol = n
+        self.k = k
+        self.asked = []
+
+    def export_rows(self, rows):
+        import numpy as np
+
+        self.asked.append(np.asarray(rows).copy())
+        r, n, k = len(rows), self.n, self.k
+        view = np.asarray(rows)[:, None] * 7 + np.arange(n)[None, :]
+        kv = view[:, :, None] + np.arange(k)[None, None, :]
+        return {"hb": view.astype(np.uint32), "fd_sum": view / 64.0, "fd_last": (view + (1 << 30)).astype(np.int64),
+                "kv_version": kv.astype(np.uint32), "kv_value_id": (kv + (1 << 24) + 1).astype(np.uint32)}
+
+
+def test_bench_dump_outputs_writes_a_fixed_sample_as_float_arrays(tmp_path):
+    """bench.py --dump-outputs: the same seeded rows and columns every time, per-view arrays over every column,
+    per-key arrays over the drawn columns, the counters in COUNTER_FIELDS order; float32 / float64 .npy files
+    that hold the exported integers exactly, within 64 MB."""
+    import numpy as np
+
+    import bench
+    from aiocluster_amd import _lib
+
+    n, k = 5000, 3
+    counters = {f: (1 << 40) + i for i, f in enumerate(_lib.COUNTER_FIELDS)}
+    sims = [_ExportOnly(n, k), _ExportOnly(n, k)]
+    shapes = [bench.dump_outputs(s, counters, str(tmp_path / f"o{i}")) for i, s in enumerate(sims)]
+    assert shapes[0] == shapes[1]
+    rows = sims[0].asked[0]
+    assert len(rows) == bench.DUMP_ROWS and np.array_equal(rows, sims[1].asked[0]) and len(set(rows.tolist())) == len(rows)
+    got = {f[:-4]: np.load(tmp_path / "o0" / f) for f in sorted(os.listdir(tmp_path / "o0"))}
+    assert set(got) == {"sample_rows", "sample_cols", "counters", "hb", "fd_sum", "fd_last", "kv_version", "kv_value_id"}
+    assert all(a.dtype in (np.float32, np.float64) for a in got.values())
+    assert sum(a.nbytes for a in got.values()) <= 64 << 20
+    cols = got["sample_cols"].astype(np.int64)
+    assert len(cols) == bench.DUMP_COLS and np.all(np.diff(cols) > 0) and cols[-1] < n
+    want = sims[0].export_rows(rows)
+    assert got["hb"].shape == (len(rows), n) and got["kv_version"].shape == (len(rows), len(cols), k)
+    assert np.array_equal(got["hb"], want["hb"]) and np.array_equal(got["fd_sum"], want["fd_sum"])
+    assert np.array_equal(got["fd_last"], want["fd_last"])  # above 2^24: binary64
+    assert np.array_equal(got["kv_value_id"], want["kv_value_id"][:, cols])
+    assert np.array_equal(got["kv_version"], want["kv_version"][:, cols])
+    assert got["counters"].tolist() == [float(counters[f]) for f in _lib.COUNTER_FIELDS]
+    for f in os.listdir(tmp_path / "o0"):
+        assert np.array_equal(np.load(tmp_path / "o0" / f), np.load(tmp_path / "o1" / f)), f

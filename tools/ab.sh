@@ -1,10 +1,11 @@
 #!/bin/bash
 # A/B bench runs in one GPU call: each VARIANT is "name:ENV=VAL,ENV=VAL" (env for bench.py), run in turn
-#   TAG=<tag> VARIANTS="base: fused:GS_PACK=fused" [ARGS="--steps 5 --warmup 2 --no-cpu-baseline"] bash tools/ab.sh
+#   TAG=<tag> VARIANTS="base: fused:GS_PACK=fused" [ARGS="--full --steps 5 --warmup 2 --no-cpu-baseline"] bash tools/ab.sh
+# (the summary line reads the peer-selected rounds and the copy ceiling: bench.py --full)
 set -o pipefail
 cd $GRAFT_REPO_ROOT
 O=gpurun_out/$TAG; mkdir -p $O
-ARGS=${ARGS:-"--steps 5 --warmup 2 --no-cpu-baseline"}
+ARGS=${ARGS:-"--full --steps 5 --warmup 2 --no-cpu-baseline"}
 for v in $VARIANTS; do
   name=${v%%:*}; envs=${v#*:}
   ( for kv in ${envs//,/ }; do export "$kv"; done

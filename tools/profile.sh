@@ -10,7 +10,7 @@ R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 TAG=$1; shift
 # the kernel-trace pass runs the driver's own round-end command by default (its line reproduces BENCH's); the PMC
 # passes skip the CPU baseline and the peer-selected rounds (after the timed region: the marker window excludes them)
-ARGS=${@:---gpus 1 --steps 20 --warmup 5}
+ARGS=${@:---gpus 1 --steps 20 --warmup 5 --full}
 PARGS=${PARGS:-$ARGS --no-cpu-baseline --peer-select-steps 0}
 OUT=$R/gpurun_out/prof_$TAG
 mkdir -p $OUT
