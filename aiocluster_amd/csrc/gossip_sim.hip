@@ -2853,7 +2853,11 @@ struct HeavyLds {
     uint32_t wcnt[HTB][HW_WAVES];
     uint32_t first, S, stop, tail, steps, groups;
     uint16_t surv[HSB];  // first-fit survivors in sender order (offsets from the super-block's start)
-    uint32_t pe[HPB];    // a whole-fit block's candidates: DeltaPb bytes | kv count << 16 | prefix views << 24
+    // a whole-fit block's candidates.  The DeltaPb bytes take a whole word: a NodeDelta of K = 16 values of 16,383
+    // bytes is ~260 KB (16 bits of it sent more than the mtu past 65,535 bytes, and read exactly 65,536 as "nothing
+    // to send").  18.5 KB of LDS per workgroup in all: HW_OCC workgroups per CU take 74 of its 160 KB
+    uint32_t pe[HPB];    // DeltaPb bytes (0: nothing to send)
+    uint16_t pk[HPB];    // kv count | prefix views << 8
     uint16_t wl[HWIN];   // a bitmap window's stale positions (offsets from the window start)
 };
 // a candidate source: pass 1's records of a row half, or a compacted bitmap window (rows read for the words)
@@ -2911,7 +2915,7 @@ __device__ __forceinline__ void heavy_eval(const Dev &d, uint32_t s, uint32_t r,
 // whole-fit prefix: candidates [pos, pos + HPB) of src (thread i: the HPK consecutive ones from pos + i HPK, those
 // < len), none of them in first-fit continuation yet.  Sends whole every candidate before the first that does not
 // fit; returns how many candidates it consumed (HPB, or that first one's offset: first-fit continuation, sh.tail,
-// resumes there).  Each candidate's size, kv count and prefix flag wait in LDS (sh.pe) through the scan; a sent
+// resumes there).  Each candidate's size, kv count and prefix flag wait in LDS (sh.pe, sh.pk) through the scan; a sent
 // prefix candidate's apply is one max_version store (none if pass 1 merged it), any other is evaluated again
 template <int KW>
 __device__ __forceinline__ uint32_t heavy_prefix(const Dev &d, uint32_t s, uint32_t r, const DigestSide &ds, uint32_t t,
@@ -2921,19 +2925,22 @@ __device__ __forceinline__ uint32_t heavy_prefix(const Dev &d, uint32_t s, uint3
     const uint32_t mtu = d.mtu, S = sh.S;
     const uint32_t q0 = pos + (uint32_t)tid * HPK;
     uint32_t *pe = sh.pe + (uint32_t)tid * HPK;
+    uint16_t *pk = sh.pk + (uint32_t)tid * HPK;
     uint32_t sum = 0;
 #pragma unroll 1
     for (uint32_t k = 0; k < HPK; k++) {
-        uint32_t x = 0u;
+        uint32_t x = 0u, y = 0u;
         if (q0 + k < len) {
             uint32_t j, m;
             hsrc_get(d, src, sh, q0 + k, s, r, j, m, st.alg);
             Cand<KW> c;
             heavy_eval<KW>(d, s, r, ds, t, j, m, lightok, c, st);
-            x = c.emsg | (c.nkv << 16) | (c.fast ? 1u << 24 : 0u);
+            x = c.emsg;
+            y = c.nkv | (c.fast ? 1u << 8 : 0u);
             sum += c.emsg;
         }
         pe[k] = x;
+        pk[k] = (uint16_t)y;
     }
     uint32_t total;
     const uint32_t ex = block_excl_scan(sum, sh, &total);
@@ -2950,7 +2957,7 @@ __device__ __forceinline__ uint32_t heavy_prefix(const Dev &d, uint32_t s, uint3
         uint32_t run = S + ex;
 #pragma unroll 1
         for (uint32_t k = 0; k < HPK; k++) {
-            const uint32_t em = pe[k] & 0xFFFFu;
+            const uint32_t em = pe[k];
             if (em && run + em > mtu) {
                 atomicMin(&sh.first, (uint32_t)tid * HPK + k);
                 break;
@@ -2961,7 +2968,7 @@ __device__ __forceinline__ uint32_t heavy_prefix(const Dev &d, uint32_t s, uint3
         f = sh.first;
         if ((uint32_t)tid == f / HPK) {  // the thread holding candidate f: the bytes before it
             uint32_t bb = S + ex;
-            for (uint32_t k = 0; k < f % HPK; k++) bb += pe[k] & 0xFFFFu;
+            for (uint32_t k = 0; k < f % HPK; k++) bb += pe[k];
             sh.S = bb;
             sh.tail = 1u;
         }
@@ -2970,8 +2977,8 @@ __device__ __forceinline__ uint32_t heavy_prefix(const Dev &d, uint32_t s, uint3
 #pragma unroll 1
     for (uint32_t k = 0; k < HPK; k++) {
         if ((uint32_t)tid * HPK + k >= f || q0 + k >= len) break;
-        const uint32_t x = pe[k], em = x & 0xFFFFu;
-        const bool fast = (x >> 24) & 1u;
+        const uint32_t em = pe[k], x = pk[k];
+        const bool fast = (x >> 8) & 1u;
         if (!em && !(merged && fast)) continue;
         uint32_t j, m;
         hsrc_get(d, src, sh, q0 + k, s, r, j, m, st.alg);  // (cache-hot)
@@ -2981,7 +2988,7 @@ __device__ __forceinline__ uint32_t heavy_prefix(const Dev &d, uint32_t s, uint3
             continue;
         }
         st.nd++;
-        st.kvs += (x >> 16) & 0xFFu;
+        st.kvs += x & 0xFFu;
         if (fast && !d.ev) {  // apply_cand's fast path: the view becomes S_j(max(ms, mr)), still a prefix
             if (!merged) {
                 const uint32_t ms = m & MV_MASK, mr = (m >> 16) & MV_MASK;
@@ -5791,6 +5798,13 @@ int gs_api_version(void) { return GS_API_VERSION; }
 
 const char *gs_last_error(const gs_handle *h) { return h ? h->err.c_str() : "null handle"; }
 
+// the largest DeltaPb NodeDelta field of an owner with K keys: every value of 16,383 bytes (gs_owner_writes refuses
+// longer ones), 255-byte keys, 3-byte versions, a status, and a NodeIdPb of 65,535 bytes (GS_R_NID_SIZE is u16)
+static uint64_t max_nodedelta(uint32_t K) {
+    const uint32_t kv = msgf(sfield(255u) + sfield((1u << 14) - 1u) + ufield(MV_MASK) + ufield(3u));
+    return msgf(msgf(0xFFFFu) + 2u * ufield(MV_MASK) + K * kv + 1u + vlen(MV_MASK));
+}
+
 int gs_create(const gs_config *cfg, gs_handle **out) {
     if (!cfg || !out) return GS_E_INVALID;
     *out = nullptr;
@@ -5808,6 +5822,12 @@ int gs_create(const gs_config *cfg, gs_handle **out) {
     if ((c.flags & GS_NO_HELD) && (c.flags & GS_TOMBSTONES)) return GS_E_INVALID;  // prefix views need no GC
     if (c.hist_cap < 2 || c.hist_cap > 255) return GS_E_INVALID;
     if (c.mtu < 1 || c.window < 1) return GS_E_INVALID;
+    // sizes ("Size limits"): the packers keep a delta's running size S in 32 bits and add to it,
+    // before comparing with the mtu, at most one first-fit block of candidates' NodeDeltas (< 2^30 bytes: 2,048
+    // owners of K <= 16 keys, or 64 of K <= 64) -- exact while the mtu is below 2^31; a slice's slot total
+    // (gs_phase_count) has 40 bits
+    if (c.mtu > 0x7FFFFFFFu) return GS_E_INVALID;
+    if (((c.flags & GS_SLICED) || G > 1) && (uint64_t)ncol * max_nodedelta(c.n_keys) >= (1ull << 40)) return GS_E_INVALID;
     if ((c.flags & GS_FD_RING) && c.ring_rows) return GS_E_INVALID;  // every row has a ring, or a sample does
     if (c.ring_rows > c.n_nodes) return GS_E_INVALID;
     if (((c.flags & GS_FD_RING) || c.ring_rows) && (c.window > (1u << 20) || c.max_interval_ticks > 0xFFFFu))

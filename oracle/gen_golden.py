@@ -9,7 +9,10 @@ TEST INFRASTRUCTURE (see ``oracle/refharness.py``).  Writes, under
   and the device/oracle size formulas;
 * ``scen_<name>.json.gz`` -- a scenario (input) plus the reference's state after
   every round (small N: full canonical state; larger N: SHA-256 per round and
-  the full final state).
+  the full final state).  A ``SCENARIOS`` entry is a (spec, rounds, cfg, full)
+  tuple for ``make_scenario``, or a callable that returns a finished scenario
+  (the large-value ones of ``tests/bigvalues.py``: SHA-256 per round and the
+  final state only, since every state carries the values).
 
 Run:  python oracle/gen_golden.py [names...]
 """
@@ -27,6 +30,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 REPO = os.path.dirname(HERE)
 sys.path.insert(0, REPO)
 sys.path.insert(0, HERE)
+sys.path.insert(0, os.path.join(REPO, "tests"))
 
 from aiocluster_amd.scenario import (  # noqa: E402
     export_digest,
@@ -37,9 +41,25 @@ from aiocluster_amd.scenario import (  # noqa: E402
     state_hash,
 )
 from aiocluster_amd.workload import WorkloadSpec  # noqa: E402
+from bigvalues import big_values, sleeper_scenario  # noqa: E402
 from refharness import RefSim, import_reference  # noqa: E402
 
 GOLDEN = os.path.join(REPO, "tests", "golden")
+
+
+def bigval6() -> dict:
+    """Cold start of 6 nodes whose values have the lengths of bigvalues.EDGES (1 .. 16,383 bytes): deletes, TTL
+    writes, tombstone GC, churn, and an mtu that cuts NodeDeltas of several 16 KB values."""
+    spec = WorkloadSpec(n=6, k=16, fanout=2, seed=61, init="cold", write_frac=0.5, delete_frac=0.15, ttl_frac=0.1,
+                        down_frac=0.3, down_rounds=3)
+    return big_values(make_scenario("bigval6", spec, 12, {"mtu": 70_000, "tombstone_grace_s": 3}))
+
+
+def bigsleep12() -> dict:
+    """Two of 12 nodes away for 5 rounds of 13-16 KB writes: whole NodeDeltas past 65,535 bytes (one of exactly
+    65,536) on their return, cut by an mtu of 300,000."""
+    return sleeper_scenario(12, 300_000, 2, 5, 3)[0]
+
 
 # name -> (spec, rounds, cfg overrides, full per-round states?)
 SCENARIOS = {
@@ -114,6 +134,9 @@ SCENARIOS = {
         {},
         "digest",
     ),
+    # values of 1 .. 16,383 bytes and NodeDeltas past 64 KiB (callables: tests/bigvalues.py)
+    "bigval6": bigval6,
+    "bigsleep12": bigsleep12,
 }
 
 
@@ -147,8 +170,14 @@ def gen_pbsize(n_cases: int = 400) -> dict:
 
 
 def gen_scenario(name: str) -> dict:
-    spec, rounds, cfg, full = SCENARIOS[name]
-    scen = make_scenario(name, spec, rounds, cfg)
+    entry = SCENARIOS[name]
+    if callable(entry):
+        scen, full = entry(), False
+        scen["name"] = name
+        rounds = len(scen["rounds"])
+    else:
+        spec, rounds, cfg, full = entry
+        scen = make_scenario(name, spec, rounds, cfg)
     sim = RefSim(scenario_node_ids(scen), scen["keys"], scen["config"], scen["init"], initial_by_owner(scen))
     states, hashes = [], []
     t0 = time.time()
@@ -196,6 +225,12 @@ def gen_scenario(name: str) -> dict:
     return scen
 
 
+def write_gz(path: str, obj) -> None:
+    """Compact JSON, gzipped without a file name or time in the header: the same input gives the same bytes."""
+    with open(path, "wb") as raw, gzip.GzipFile(filename="", fileobj=raw, mode="wb", mtime=0) as f:
+        f.write(json.dumps(obj, separators=(",", ":")).encode())
+
+
 def main(argv):
     os.makedirs(GOLDEN, exist_ok=True)
     names = argv or ["pbsize", *SCENARIOS]
@@ -205,9 +240,7 @@ def main(argv):
                 json.dump(gen_pbsize(), f, separators=(",", ":"))
             print("pbsize: ok")
             continue
-        scen = gen_scenario(name)
-        with gzip.open(os.path.join(GOLDEN, f"scen_{name}.json.gz"), "wt") as f:
-            json.dump(scen, f, separators=(",", ":"))
+        write_gz(os.path.join(GOLDEN, f"scen_{name}.json.gz"), gen_scenario(name))
 
 
 if __name__ == "__main__":

@@ -9,7 +9,8 @@ from rowcheck import compare_exports  # noqa: F401  (re-exported for the tests)
 from aiocluster_amd.scenario import initial_by_owner, replay, scenario_node_ids, state_hash
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-SCENARIOS = ["simple3", "trunc8", "sched16", "fdgc12", "q9x10", "cold64", "warm128", "cold256"]
+SCENARIOS = ["simple3", "trunc8", "sched16", "fdgc12", "q9x10", "cold64", "warm128", "cold256",
+             "bigval6", "bigsleep12"]  # values up to 16,383 bytes, NodeDeltas past 64 KiB (tests/bigvalues.py)
 
 
 def load_scenario(name):

@@ -57,6 +57,32 @@ def test_create_validates_config_without_gpu():
     assert lib.gs_create(ctypes.byref(bad), ctypes.byref(h)) == -1
 
 
+def test_create_refuses_sizes_past_the_32_and_40_bit_fields():
+    """DESIGN.md section 3, "Size limits": the running size of a delta is 32 bits and takes a block of NodeDeltas
+    before it meets the mtu, so the mtu stays below 2^31; a slice's slot total has 40 bits, so a sliced handle's
+    owner columns x the largest NodeDelta (16,383-byte values) stay below 2^40."""
+    if not os.path.exists(_lib.LIB_PATH):
+        pytest.skip("library not built")
+    from aiocluster_amd.scenario import DEFAULT_CFG
+    from aiocluster_amd.sim import make_config
+
+    lib = _lib.load()
+    h = ctypes.c_void_p()
+    for mtu, rc in ((1, 0), (3_000_000, 0), ((1 << 31) - 1, 0), (1 << 31, -1), ((1 << 32) - 1, -1)):
+        c = make_config(1000, 16, dict(DEFAULT_CFG, mtu=mtu), 0, 32)
+        assert lib.gs_create(ctypes.byref(c), ctypes.byref(h)) == rc, mtu
+        if rc == 0:
+            lib.gs_destroy(h)
+    sliced = _lib.GS_CANONICAL | _lib.GS_SLICED
+    for n, k, flags, shards, rc in ((1 << 20, 59, sliced, 1, 0), (1 << 20, 60, sliced, 1, -1),
+                                    (1 << 20, 64, sliced, 1, -1), (1 << 20, 64, _lib.GS_CANONICAL, 1, 0),
+                                    (1 << 20, 64, _lib.GS_CANONICAL, 2, 0), (1_032_576, 60, sliced, 1, 0)):
+        c = make_config(n, k, DEFAULT_CFG, flags, 32, shards=shards)
+        assert lib.gs_create(ctypes.byref(c), ctypes.byref(h)) == rc, (n, k, flags, shards)
+        if rc == 0:
+            lib.gs_destroy(h)
+
+
 def test_window_layout_and_16_bit_tick_bounds():
     """Sampling windows: u32 sum|count + u16 last-report tick + state byte (+ u32 time of death); gs_create
     refuses configs under which a window silent for 2^15 ticks could still append an interval

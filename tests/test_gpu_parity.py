@@ -35,7 +35,7 @@ def test_gpu_matches_reference_golden(name):
     assert c["q9"] == len(exp["q9"])  # garbage_collect KeyErrors
 
 
-SET_ONLY = ["sched16", "fdgc12", "q9x10", "warm128"]  # golden scenarios without deletes / TTL writes
+SET_ONLY = ["sched16", "fdgc12", "q9x10", "warm128", "bigsleep12"]  # golden scenarios without deletes / TTL writes
 
 
 @pytest.mark.parametrize("name", SET_ONLY)

@@ -20,7 +20,8 @@ from aiocluster_amd.wire import WireEmitter
 pytestmark = pytest.mark.gpu
 
 CASES = [("trunc8", True), ("sched16", True), ("fdgc12", True), ("simple3", True), ("cold64", True),
-         ("sched16", False), ("fdgc12", False)]
+         ("sched16", False), ("fdgc12", False),
+         ("bigval6", True), ("bigsleep12", True), ("bigsleep12", False)]  # 3-byte length prefixes, 64 KiB NodeDeltas
 
 
 @pytest.mark.parametrize("name,tomb", CASES)

@@ -18,7 +18,7 @@ from aiocluster_amd.pbsize import nodeid_size
 from aiocluster_amd.scenario import scenario_node_ids
 from aiocluster_amd.wire import frame, node_id_pb, packet, varint
 
-NAMES = ["trunc8", "sched16", "fdgc12", "simple3", "cold64"]
+NAMES = ["trunc8", "sched16", "fdgc12", "simple3", "cold64", "bigval6", "bigsleep12"]
 
 
 def load_wire(name):
@@ -67,6 +67,33 @@ def test_delta_fixture_structure():
                 assert vers == sorted(vers)
                 seen_trunc |= len(vers) == 0
     assert not seen_trunc  # a NodeDelta is only sent with at least one kv (state.py:403)
+
+
+@pytest.mark.parametrize("name", ["bigval6", "bigsleep12"])
+def test_large_value_fixtures_hold_long_bodies_and_mtu_cuts(name):
+    """What the large-value wire fixtures are for: a NodeDelta body of 16,384 bytes or more (a 3-byte length
+    prefix) and a NodeDelta the mtu cut; bigsleep12 also a NodeDelta field of 65,536 bytes or more and one of
+    exactly 65,536 (tests/bigvalues.py: the designated owner's)."""
+    w = load_wire(name)
+    assert w["truncated"] and all(0 <= i < len(w["cases"]) for i in w["truncated"])
+    bodies, values = [], []
+    for _, _, _, _, dhex in w["cases"]:
+        for num, _, nd in fields(bytes.fromhex(dhex)):
+            bodies.append(len(nd))
+            values += [len(g[2]) for f in fields(nd) if f[0] == 4 for g in fields(f[2]) if g[0] == 2]
+    assert max(bodies) >= 1 << 14
+    assert max(values) == (1 << 14) - 1 or name != "bigval6"  # the value limit itself is on the wire
+    if name == "bigsleep12":
+        fld = [1 + len(varint(b)) + b for b in bodies]  # the node_deltas field: tag, length, body
+        assert max(fld) > 1 << 16 and (1 << 16) in fld
+        # SET only: a NodeDelta whose last kv is below its max_version was cut by the mtu
+        cut = 0
+        for i in w["truncated"]:
+            for _, _, nd in fields(bytes.fromhex(w["cases"][i][4])):
+                sub = fields(nd)
+                vers = [dict((g[0], g[2]) for g in fields(f[2])).get(3, 0) for f in sub if f[0] == 4]
+                cut += vers[-1] < sub[-1][2]
+        assert cut >= len(w["truncated"])
 
 
 def test_packet_kinds_and_frame():
