@@ -1,8 +1,9 @@
 """Backend-neutral scenario format and replay loop.
 
 A *scenario* is plain JSON-able data: node identities, key names, hot-path
-configuration, boot writes and, per round, the owner writes, the up-mask and
-the explicit phase schedule.  The same scenario is replayed by
+configuration, boot writes and, per round, the owner writes, the up-mask, the
+explicit phase schedule and, optionally, the ticks of its phases (``round_ticks``).
+The same scenario is replayed by
 
 * the reference harness (``oracle/refharness.py``, container only) to make
   golden fixtures,
@@ -19,7 +20,7 @@ import hashlib
 import json
 
 from .entities import NodeId
-from .workload import Workload, WorkloadSpec, liveness_tick, phase_tick, round_tick
+from .workload import TICKS_PER_ROUND, Workload, WorkloadSpec, liveness_tick, phase_tick, round_tick
 
 DEFAULT_CFG = {
     "mtu": 65_507,  # Config.max_payload_size (entities.py:105)
@@ -113,14 +114,35 @@ def replay(backend, scen: dict, on_round=None, rounds: int | None = None):
             on_round(r)
 
 
+def round_ticks(scen: dict, r: int) -> list[int]:
+    """The ticks of round ``r``'s phases, then of its liveness sweep.  A round may carry ``"ticks"``: one offset
+    from ``round_tick(r)`` per phase and one for the sweep -- non-decreasing, the first >= 1, none past the round's
+    last tick; equal offsets are phases at one time (sub-phases).  Without it: ``phase_tick`` / ``liveness_tick``."""
+    rd = scen["rounds"][r]
+    P = len(rd["phases"])
+    offs = rd.get("ticks")
+    if offs is None:
+        return [phase_tick(r, p) for p in range(P)] + [liveness_tick(r, P)]
+    if len(offs) != P + 1:
+        raise ValueError(f"round {r}: ticks has {len(offs)} offsets for {P} phases + the liveness sweep")
+    prev = 1
+    for i, o in enumerate(offs):
+        if not isinstance(o, int) or o < prev or o > TICKS_PER_ROUND - 1:
+            raise ValueError(f"round {r}: ticks[{i}] = {o!r} is not an integer in [{prev}, {TICKS_PER_ROUND - 1}] "
+                             f"(offsets are non-decreasing, from 1, within the round)")
+        prev = o
+    return [round_tick(r) + o for o in offs]
+
+
 def replay_round(backend, scen: dict, r: int):
     """Round ``r`` of ``scen`` on ``backend`` (writes, round start, phases, liveness)."""
     rd = scen["rounds"][r]
     t = round_tick(r)
     up = rd["up"]
+    ticks = round_ticks(scen, r)  # checked before the backend sees anything of the round
     for j, k, op, v in rd["writes"]:
         backend.write(t, j, k, op, v)
     backend.begin_round(t, up)
     for p, ph in enumerate(rd["phases"]):
-        backend.run_phase(phase_tick(r, p), ph)
-    backend.liveness(liveness_tick(r, len(rd["phases"])), up, r)
+        backend.run_phase(ticks[p], ph)
+    backend.liveness(ticks[-1], up, r)

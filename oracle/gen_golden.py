@@ -12,7 +12,8 @@ TEST INFRASTRUCTURE (see ``oracle/refharness.py``).  Writes, under
   the full final state).  A ``SCENARIOS`` entry is a (spec, rounds, cfg, full)
   tuple for ``make_scenario``, or a callable that returns a finished scenario
   (the large-value ones of ``tests/bigvalues.py``: SHA-256 per round and the
-  final state only, since every state carries the values).
+  final state only, since every state carries the values; the many-phase ones of
+  ``tests/manyphases.py``, whose rounds carry explicit ``"ticks"``).
 
 Run:  python oracle/gen_golden.py [names...]
 """
@@ -42,6 +43,7 @@ from aiocluster_amd.scenario import (  # noqa: E402
 )
 from aiocluster_amd.workload import WorkloadSpec  # noqa: E402
 from bigvalues import big_values, sleeper_scenario  # noqa: E402
+from manyphases import subfront40, subring24  # noqa: E402
 from refharness import RefSim, import_reference  # noqa: E402
 
 GOLDEN = os.path.join(REPO, "tests", "golden")
@@ -137,7 +139,12 @@ SCENARIOS = {
     # values of 1 .. 16,383 bytes and NodeDeltas past 64 KiB (callables: tests/bigvalues.py)
     "bigval6": bigval6,
     "bigsleep12": bigsleep12,
+    # rounds of 13-95 phases with several phases at one tick (callables: tests/manyphases.py); subring24 keeps the
+    # state of every round (ring windows of 5, max_interval 0.25 s), subfront40 hashes and the final state
+    "subring24": subring24,
+    "subfront40": subfront40,
 }
+FULL_STATES = {"subring24"}  # callables whose fixture stores every round's state
 
 
 def gen_pbsize(n_cases: int = 400) -> dict:
@@ -172,7 +179,7 @@ def gen_pbsize(n_cases: int = 400) -> dict:
 def gen_scenario(name: str) -> dict:
     entry = SCENARIOS[name]
     if callable(entry):
-        scen, full = entry(), False
+        scen, full = entry(), name in FULL_STATES
         scen["name"] = name
         rounds = len(scen["rounds"])
     else:
