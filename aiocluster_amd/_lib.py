@@ -87,10 +87,10 @@ EXPORTS = [
     "gs_select_peers", "gs_schedule_phases", "gs_set_events", "gs_emit_scratch_bytes", "gs_emit_digest", "gs_emit_delta",
     "gs_check_heartbeat_lag", "gs_stream_copy", "gs_stream_read", "gs_stream_write", "gs_set_timing", "gs_kernel_times",
     "gs_phase_overflow", "gs_phase_chain", "gs_phase_pending", "gs_comm_id", "gs_comm_init", "gs_run_phase_group", "gs_read_rows",
-    "gs_latest_tick", "gs_flush_reports", "gs_set_ring_rows", "gs_mark",
+    "gs_latest_tick", "gs_flush_reports", "gs_set_ring_rows", "gs_mark", "gs_view_census",
 ]
 
-API_VERSION = 20
+API_VERSION = 21
 MAX_PHASES = 64  # GS_MAX_PHASES
 MAX_SCHED_PHASES = 65536  # GS_MAX_SCHED_PHASES
 
@@ -138,6 +138,24 @@ class GsKtimes(C.Structure):
 
 class GsCensus(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in CENSUS_FIELDS]
+
+
+# gs_view_census (include/gossip_sim.h)
+GS_VC_HEARTBEATS = 1
+GS_VC_MAX_PROBES = 64
+GS_VC_BUCKETS = 20
+VIEW_TOTAL_FIELDS = ["observers", "views", "unknown", "behind", "inexact", "max_version_lag", "max_heartbeat_lag"]
+VIEW_MAX_FIELDS = ("max_version_lag", "max_heartbeat_lag")  # maxima over the slices, not sums
+VIEW_HIST_FIELDS = ["version_lag_hist", "heartbeat_lag_hist"]
+
+
+class GsProbe(C.Structure):
+    _fields_ = [("owner", C.c_uint32), ("version", C.c_uint32)]
+
+
+class GsViewTotals(C.Structure):
+    _fields_ = ([(n, C.c_uint64) for n in VIEW_TOTAL_FIELDS] + [(n, C.c_uint64 * GS_VC_BUCKETS) for n in VIEW_HIST_FIELDS]
+                + [("reserved", C.c_uint64 * 9)])
 
 
 class GsWire(C.Structure):
@@ -227,6 +245,7 @@ def load():
         "gs_phase_pack": (C.c_int, [P, P, P, u32, u32, u32, P, P, P]),
         "gs_materialize_held": (C.c_int, [P, u32, u32]),
         "gs_fd_census": (C.c_int, [P, P, C.POINTER(GsCensus)]),
+        "gs_view_census": (C.c_int, [P, P, u32, C.POINTER(GsProbe), u32, C.POINTER(u64), P, P, C.POINTER(GsViewTotals)]),
         "gs_set_events": (C.c_int, [P, P, u32, P]),
         "gs_select_peers": (C.c_int, [P, P, u32, P, u32, C.c_uint64, u32, P, P]),
         "gs_schedule_phases": (C.c_int, [P, P, u32, P, C.c_uint64, u32, u32, u32, P, P, P, C.POINTER(u32),

@@ -4313,6 +4313,359 @@ __global__ __launch_bounds__(LB) void k_hot_clear(Dev d) {
     if (i < d.NP / 16u) d.p1flags[i] &= 0xFFFFu;
 }
 
+// Dissemination census (gs_view_census): a read-only streaming pass over GS_R_MV (and, with GS_VC_HEARTBEATS,
+// GS_R_HB) that counts, over the observer rows with up[o] != 0, the known / unknown / behind / inexact views, the
+// version- and heartbeat-lag histograms and maxima, per owner column {behind, unknown, max version lag}, per
+// observer row the columns it is behind on or does not know, and the reach of up to GS_VC_MAX_PROBES
+// (owner, version) probes.
+// One workgroup per (band of VC_BAND consecutive observer rows, column chunk of LB x PER columns), as k_hb_lag:
+// one 16-byte non-temporal load per thread, row and region, VC_AHEAD rows in flight while one is reduced; the
+// owners' own values, escape slots and the probes are loaded once per workgroup.  Everything a thread counts stays
+// in registers over the band (per-owner counts, packed histogram fields of VC_HBITS bits), so a band costs at most
+// one atomic per (column, plane), per histogram bucket and per row of the chunk, zeros skipped.  All results are
+// integer sums and maxima: they do not depend on scheduling.
+// VC_BAND = 256: 65,536 x 65,536 views in chunks of 4,096 columns make 256 x 16 = 4,096 workgroups (16 per CU).
+constexpr uint32_t VC_BAND = 256;
+constexpr uint32_t VC_HBITS = 13;  // a thread counts at most VC_BAND x 16 = 2^12 views per band
+static_assert(VC_BAND * 16u < (1u << VC_HBITS), "packed histogram fields");
+// gs_view_census's device scratch (gs_handle::vc_buf): u64 accumulators, then the probes as {local column, version}
+enum VcSlot {
+    VC_OBS = 0, VC_VIEWS, VC_UNK, VC_BEHIND, VC_INEX, VC_MAXV, VC_MAXH,
+    VC_VH, VC_HH = VC_VH + GS_VC_BUCKETS, VC_REACH = VC_HH + GS_VC_BUCKETS, VC_NUM = VC_REACH + GS_VC_MAX_PROBES
+};
+struct VcArgs {
+    const uint8_t *up;         // nullptr: every row counts
+    uint32_t flags, n_probes;
+    unsigned long long *acc;   // [VC_NUM], zeroed
+    const uint32_t *probes;    // [n_probes][2] {local column or NONE, version}
+    uint32_t *owners, *rows;   // optional outputs, zeroed
+};
+__device__ __forceinline__ uint32_t wave_sum32(uint32_t x) {
+#pragma unroll
+    for (int dd = 32; dd >= 1; dd >>= 1) x += __shfl_xor(x, dd, WAVE);
+    return x;
+}
+__device__ __forceinline__ uint32_t wave_max32(uint32_t x) {
+#pragma unroll
+    for (int dd = 32; dd >= 1; dd >>= 1) x = max(x, (uint32_t)__shfl_xor(x, dd, WAVE));
+    return x;
+}
+// lag bucket (GS_VC_BUCKETS): 0 for lag 0, else min(19, bit length)
+__device__ __forceinline__ uint32_t vc_bucket(uint32_t lag) { return min(GS_VC_BUCKETS - 1u, 32u - (uint32_t)__clz(lag)); }
+// bit 7 of each byte -> the whole byte
+__device__ __forceinline__ uint32_t bytes7(uint32_t b7) { return (b7 >> 7) * 0xFFu; }
+// per-byte maximum of two words whose bytes are all < 2^7
+__device__ __forceinline__ uint32_t bmax7(uint32_t x, uint32_t y) {
+    const uint32_t ge = bytes7(((x | B7) - y) & B7);  // bytes where x >= y
+    return (x & ge) | (y & ~ge);
+}
+constexpr uint32_t VC_AHEAD = 3;  // rows in flight per thread: 16 waves per CU x 3 rows x 16 B per lane and region
+template <bool SWAR>
+__global__ __launch_bounds__(LB, 4) void k_view_census(Dev d, VcArgs a, uint32_t chunks) {
+    constexpr uint32_t PER = SWAR ? 16u : 8u;  // views per thread and row: one 16-byte load of the widest region
+    __shared__ uint32_t s_hist[2][GS_VC_BUCKETS];
+    __shared__ uint32_t s_rows[VC_BAND];
+    __shared__ uint32_t s_pi[GS_VC_MAX_PROBES];
+    __shared__ uint32_t s_pn;
+    // SWAR: an escaped column's own heartbeat mod 2^16 | slot << 16, per thread and column (read only for escaped
+    // columns, so it lives here and not in registers)
+    __shared__ uint32_t s_escpk[SWAR ? 16 : 1][LB];
+    const bool genm = !(d.flags & GS_CANONICAL);
+    const bool wantH = a.flags & GS_VC_HEARTBEATS;
+    const uint32_t tid = threadIdx.x;
+    const uint32_t rb = blockIdx.x / chunks, cb = blockIdx.x % chunks;
+    const uint32_t c_lo = cb * LB * PER, j0 = c_lo + tid * PER;
+    const uint32_t o0 = rb * VC_BAND, nrow = min(VC_BAND, d.N - o0);
+    const bool act = j0 < d.ncol;
+    const uint32_t nvt = act ? min(d.ncol - j0, PER) : 0u;  // this thread's real columns (padding is never counted)
+    for (uint32_t i = tid; i < 2u * GS_VC_BUCKETS; i += LB) (&s_hist[0][0])[i] = 0u;
+    for (uint32_t i = tid; i < VC_BAND; i += LB) s_rows[i] = 0u;
+    if (tid == 0) s_pn = 0u;
+    __syncthreads();
+    // the probes whose owner column lies in this chunk (none: the probes cost this workgroup nothing more)
+    if (tid < a.n_probes) {
+        const uint32_t c = a.probes[2u * tid];
+        if (c != NONE && c >= c_lo && c < c_lo + LB * PER) s_pi[atomicAdd(&s_pn, 1u)] = tid;
+    }
+    __syncthreads();
+    const uint32_t npc = s_pn;
+    uint32_t p_i = 0, p_c = 0, p_v = 0, p_M = 0, p_reach = 0;  // thread i < npc counts probe s_pi[i] over the band
+    if (tid < npc) {
+        p_i = s_pi[tid];
+        p_c = a.probes[2u * p_i];
+        p_v = a.probes[2u * p_i + 1u];
+        p_M = d.self_mv[p_c];
+    }
+    // the owners' own values and escape slots: the same for every row of the band
+    uint32_t own8v[4], owm7v[4], vm7v[4], esc7v[4];  // SWAR: four columns per word (k_hb_lag)
+    uint32_t ownR[SWAR ? 1 : 8], ownM[SWAR ? 1 : 8], slot[SWAR ? 1 : 8];  // per column
+    if constexpr (SWAR) {
+#pragma unroll
+        for (uint32_t q = 0; q < 4u; q++) {
+            const uint32_t jq = j0 + 4u * q;
+            own8v[q] = owm7v[q] = vm7v[q] = esc7v[q] = 0u;
+            if (jq >= d.ncol) continue;
+            const uint4 pk = *reinterpret_cast<const uint4 *>(d.self_pk + jq);
+            own8v[q] = (pk.x & 0xFFu) | ((pk.y & 0xFFu) << 8) | ((pk.z & 0xFFu) << 16) | (pk.w << 24);
+            owm7v[q] = ((pk.x >> 16) & 0x7Fu) | (((pk.y >> 16) & 0x7Fu) << 8) | (((pk.z >> 16) & 0x7Fu) << 16) |
+                       (((pk.w >> 16) & 0x7Fu) << 24);
+            const uint32_t nv = min(d.ncol - jq, 4u);
+            vm7v[q] = nv >= 4u ? B7 : B7 & ((1u << (8u * nv)) - 1u);  // bit 7 of the real columns
+            if (d.EC && wantH) {
+                uint32_t es[4], R[4];
+                ld4(d.esc_slot + jq, es);
+                ld4(d.self_hb + jq, R);
+#pragma unroll
+                for (uint32_t i = 0; i < 4; i++) {
+                    if (es[i] == NONE) continue;
+                    esc7v[q] |= 0x80u << (8u * i);
+                    s_escpk[4u * q + i][tid] = (R[i] & 0xFFFFu) | (es[i] << 16);  // (read back by this thread only)
+                }
+                esc7v[q] &= vm7v[q];
+            }
+        }
+    } else {
+#pragma unroll
+        for (uint32_t q = 0; q < 2u; q++) {
+            const uint32_t jq = j0 + 4u * q;
+            uint32_t R[4] = {0u, 0u, 0u, 0u}, M[4] = {0u, 0u, 0u, 0u}, es[4] = {NONE, NONE, NONE, NONE};
+            if (jq < d.ncol) {
+                ld4(d.self_hb + jq, R);
+                ld4(d.self_mv + jq, M);
+                if (d.EC) ld4(d.esc_slot + jq, es);
+            }
+#pragma unroll
+            for (uint32_t i = 0; i < 4; i++) { ownR[4u * q + i] = R[i]; ownM[4u * q + i] = M[i]; slot[4u * q + i] = es[i]; }
+        }
+    }
+    // one 16-byte load per region and row (8 bytes where this path's 8 views are bytes), VC_AHEAD rows ahead
+    v4u_t bh[VC_AHEAD], bm[VC_AHEAD];
+    auto ldv = [&](uint32_t o, v4u_t &nh, v4u_t &nm) {
+        nh = nm = v4u_t{0u, 0u, 0u, 0u};
+        if (!act) return;
+        const size_t p0 = pix(d, o, j0);
+        const uint8_t *m8 = reinterpret_cast<const uint8_t *>(d.mv), *h8 = reinterpret_cast<const uint8_t *>(d.hb);
+        if (SWAR) {
+            nm = __builtin_nontemporal_load(reinterpret_cast<const v4u_t *>(m8 + p0));
+            if (wantH) nh = __builtin_nontemporal_load(reinterpret_cast<const v4u_t *>(h8 + p0));
+            return;
+        }
+        if (d.mv8) {
+            const v2u_t x = __builtin_nontemporal_load(reinterpret_cast<const v2u_t *>(m8 + p0));
+            nm.x = x.x; nm.y = x.y;
+        } else {
+            nm = __builtin_nontemporal_load(reinterpret_cast<const v4u_t *>(d.mv + p0));
+        }
+        if (!wantH) return;
+        if (d.hb8) {
+            const v2u_t x = __builtin_nontemporal_load(reinterpret_cast<const v2u_t *>(h8 + p0));
+            nh.x = x.x; nh.y = x.y;
+        } else {
+            nh = __builtin_nontemporal_load(reinterpret_cast<const v4u_t *>(d.hb + p0));
+        }
+    };
+#pragma unroll
+    for (uint32_t u = 0; u < VC_AHEAD; u++) ldv(o0 + min(u, nrow - 1u), bh[u], bm[u]);
+    uint32_t t_views = 0, t_unk = 0, t_inex = 0, t_maxh = 0, n_obs = 0;
+    // per owner column, over the band.  SWAR: behind counts as bytes (widened to 16-bit pairs every 128 rows: beh[2 q]
+    // holds columns 4 q and 4 q + 2, beh[2 q + 1] columns 4 q + 1 and 4 q + 3), largest lags as bytes (mxv[q])
+    uint32_t beh[8], unk[SWAR ? 1 : 8], mxv[SWAR ? 4 : 8];
+    uint32_t beh8[4] = {0u, 0u, 0u, 0u};
+    // histogram fields of VC_HBITS bits: buckets 1-4 and 5-8 (SWAR: every lag < 2^8); the other path keeps buckets
+    // 1-4 here and sends the rare wider lags to the workgroup's LDS histogram
+    unsigned long long vlo = 0ull, vhi = 0ull, hlo = 0ull, hhi = 0ull;
+#pragma unroll
+    for (uint32_t k = 0; k < 8u; k++) beh[k] = 0u;
+#pragma unroll
+    for (uint32_t k = 0; k < (SWAR ? 4u : 8u); k++) mxv[k] = 0u;
+#pragma unroll
+    for (uint32_t k = 0; k < (SWAR ? 1u : 8u); k++) unk[k] = 0u;
+    auto hadd = [&](unsigned long long &lo, unsigned long long &hi, uint32_t pl, uint32_t lag) {
+        const uint32_t b = vc_bucket(lag) - 1u;  // lag != 0
+        const unsigned long long inc = 1ull << (VC_HBITS * (b & 3u));
+        if (b < 4u) lo += inc;
+        else if (SWAR && b < 8u) hi += inc;
+        else atomicAdd(&s_hist[pl][b + 1u], 1u);
+    };
+    // one row of the band: hr / mr = this thread's views of observer o
+    auto row = [&](uint32_t r, const v4u_t hr, const v4u_t mr) {
+        const uint32_t o = o0 + r;
+        const bool counted = !a.up || a.up[o];
+        if (counted) {
+            n_obs++;
+            uint32_t rowc = 0;  // this thread's columns the row is behind on or does not know
+            if (act) {
+                const uint32_t hw[4] = {hr.x, hr.y, hr.z, hr.w}, mw[4] = {mr.x, mr.y, mr.z, mr.w};
+                if constexpr (SWAR) {
+                    t_views += nvt;
+#pragma unroll
+                    for (uint32_t q = 0; q < 4u; q++) {
+                        const uint32_t vm7 = vm7v[q], vmask = bytes7(vm7);
+                        t_inex += (uint32_t)__popc(mw[q] & vm7);
+                        const uint32_t lagM = ((owm7v[q] | B7) - (mw[q] & L7)) & L7 & vmask;  // (own - view) mod 2^7
+                        if (lagM) {  // only non-zero lags go one view at a time (the histogram)
+                            const uint32_t nz = (lagM + L7) & B7;
+                            beh8[q] += nz >> 7;
+                            rowc += (uint32_t)__popc(nz);
+                            mxv[q] = bmax7(mxv[q], lagM);
+#pragma unroll
+                            for (uint32_t i = 0; i < 4; i++) {
+                                const uint32_t l = (lagM >> (8u * i)) & 0x7Fu;
+                                if (l) hadd(vlo, vhi, 0u, l);
+                            }
+                        }
+                        if (!wantH) continue;
+                        const uint32_t esc7 = esc7v[q];
+                        const uint32_t lagH = bsub(own8v[q], hw[q]) & vmask & ~bytes7(esc7);  // (own - view) mod 2^8
+                        if (lagH) {
+#pragma unroll
+                            for (uint32_t i = 0; i < 4; i++) {
+                                const uint32_t l = (lagH >> (8u * i)) & 0xFFu;
+                                if (!l) continue;
+                                t_maxh = max(t_maxh, l);
+                                hadd(hlo, hhi, 1u, l);
+                            }
+                        }
+                        if (esc7) {  // escaped columns: 16-bit views in GS_R_ESC16, one at a time
+#pragma unroll
+                            for (uint32_t i = 0; i < 4; i++) {
+                                if (!((esc7 >> (8u * i + 7u)) & 1u)) continue;
+                                const uint32_t pk = s_escpk[4u * q + i][tid];
+                                const uint32_t l = (pk - d.esc16[(size_t)o * d.EC + (pk >> 16)]) & 0xFFFFu;
+                                if (!l) continue;
+                                t_maxh = max(t_maxh, l);
+                                atomicAdd(&s_hist[1][vc_bucket(l)], 1u);
+                            }
+                        }
+                    }
+                } else {
+                    const size_t p0 = pix(d, o, j0);
+                    uint32_t ps[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
+                    if (genm) {
+                        const uint4 x = *reinterpret_cast<const uint4 *>(d.pos + p0), y = *reinterpret_cast<const uint4 *>(d.pos + p0 + 4);
+                        ps[0] = x.x; ps[1] = x.y; ps[2] = x.z; ps[3] = x.w; ps[4] = y.x; ps[5] = y.y; ps[6] = y.z; ps[7] = y.w;
+                    }
+#pragma unroll
+                    for (uint32_t k = 0; k < 8u; k++) {
+                        if (k >= nvt) continue;
+                        if (genm && ps[k] == NONE) {
+                            unk[SWAR ? 0 : k]++;
+                            t_unk++;
+                            rowc++;
+                            continue;
+                        }
+                        t_views++;
+                        const uint32_t w = d.mv8 ? mv_dec8((mw[k >> 2] >> (8u * (k & 3u))) & 0xFFu, ownM[SWAR ? 0 : k])
+                                                 : (mw[k >> 1] >> (16u * (k & 1u))) & 0xFFFFu;
+                        t_inex += w >> 15;
+                        const uint32_t l = ownM[SWAR ? 0 : k] - (w & MV_MASK);
+                        if (l) {
+                            beh[k]++;
+                            rowc++;
+                            mxv[SWAR ? 0 : k] = max(mxv[SWAR ? 0 : k], l);
+                            hadd(vlo, vhi, 0u, l);
+                        }
+                        if (!wantH) continue;
+                        uint32_t lh;
+                        const uint32_t R = ownR[SWAR ? 0 : k], sl = slot[SWAR ? 0 : k];
+                        if (sl != NONE) lh = (R - d.esc16[(size_t)o * d.EC + sl]) & 0xFFFFu;
+                        else if (d.hb8) lh = (R - ((hw[k >> 2] >> (8u * (k & 3u))) & 0xFFu)) & 0xFFu;
+                        else lh = (R - ((hw[k >> 1] >> (16u * (k & 1u))) & 0xFFFFu)) & 0xFFFFu;
+                        if (lh) {
+                            t_maxh = max(t_maxh, lh);
+                            hadd(hlo, hhi, 1u, lh);
+                        }
+                    }
+                }
+            }
+            if (a.rows && __ballot(rowc != 0u)) {  // one wave reduction; one global atomic per (row, chunk) below
+                const uint32_t s = wave_sum32(rowc);
+                if ((tid & 63u) == 0u && s) atomicAdd(&s_rows[r], s);
+            }
+            if (tid < npc) {
+                const size_t p = pix(d, o, p_c);
+                if (!genm || d.pos[p] != NONE) {
+                    const uint32_t w = d.mv8 ? mv_dec8(reinterpret_cast<const uint8_t *>(d.mv)[p], p_M) : (uint32_t)d.mv[p];
+                    p_reach += (w & MV_MASK) >= p_v;
+                }
+            }
+        }
+        if constexpr (SWAR) {
+            if ((r & 127u) == 127u || r + 1u == nrow) {  // byte counters hold 128 rows: widen to 16-bit pairs
+#pragma unroll
+                for (uint32_t q = 0; q < 4u; q++) {
+                    beh[2u * q] += beh8[q] & 0x00FF00FFu;
+                    beh[2u * q + 1u] += (beh8[q] >> 8) & 0x00FF00FFu;
+                    beh8[q] = 0u;
+                }
+            }
+        }
+    };
+    for (uint32_t r0 = 0; r0 < nrow; r0 += VC_AHEAD) {
+#pragma unroll
+        for (uint32_t u = 0; u < VC_AHEAD; u++) {
+            const uint32_t r = r0 + u;
+            if (r >= nrow) break;
+            const v4u_t hr = bh[u], mr = bm[u];
+            ldv(o0 + min(r + VC_AHEAD, nrow - 1u), bh[u], bm[u]);  // (past the band: the last row again, unused)
+            row(r, hr, mr);
+        }
+    }
+    // the band's results: at most one atomic per (column, plane), zeros skipped
+    uint32_t t_beh = 0, t_maxv = 0;
+#pragma unroll
+    for (uint32_t k = 0; k < PER; k++) {
+        uint32_t bk, mk, uk = 0u;
+        if constexpr (SWAR) {  // column k = 4 q + i: count in beh[2 q + (i & 1)], half i >> 1; lag in byte i of mxv[q]
+            bk = (beh[2u * (k >> 2) + (k & 1u)] >> (16u * ((k >> 1) & 1u))) & 0xFFFFu;
+            mk = (mxv[k >> 2] >> (8u * (k & 3u))) & 0xFFu;
+        } else {
+            bk = beh[k & 7u];
+            mk = mxv[SWAR ? 0 : (k & 7u)];
+            uk = unk[SWAR ? 0 : (k & 7u)];
+        }
+        t_beh += bk;
+        t_maxv = max(t_maxv, mk);
+        if (!a.owners || k >= nvt) continue;
+        if (bk) atomicAdd(&a.owners[j0 + k], bk);
+        if (uk) atomicAdd(&a.owners[d.ncol + j0 + k], uk);
+        if (mk) atomicMax(&a.owners[2u * d.ncol + j0 + k], mk);
+    }
+#pragma unroll
+    for (uint32_t b = 0; b < 4u; b++) {
+        const uint32_t m = (1u << VC_HBITS) - 1u, sh = VC_HBITS * b;
+        const uint32_t c0 = (uint32_t)(vlo >> sh) & m, c1 = (uint32_t)(vhi >> sh) & m;
+        const uint32_t c2 = (uint32_t)(hlo >> sh) & m, c3 = (uint32_t)(hhi >> sh) & m;
+        if (c0) atomicAdd(&s_hist[0][1u + b], c0);
+        if (c1) atomicAdd(&s_hist[0][5u + b], c1);
+        if (c2) atomicAdd(&s_hist[1][1u + b], c2);
+        if (c3) atomicAdd(&s_hist[1][5u + b], c3);
+    }
+    {
+        const uint32_t lane0 = (tid & 63u) == 0u;
+        const unsigned long long sv = wave_sum(t_views), su = wave_sum(t_unk), sb = wave_sum(t_beh), si = wave_sum(t_inex);
+        const uint32_t mv_ = wave_max32(t_maxv), mh_ = wave_max32(t_maxh);
+        if (lane0) {
+            if (sv) atomicAdd(&a.acc[VC_VIEWS], sv);
+            if (su) atomicAdd(&a.acc[VC_UNK], su);
+            if (sb) atomicAdd(&a.acc[VC_BEHIND], sb);
+            if (si) atomicAdd(&a.acc[VC_INEX], si);
+            if (mv_) atomicMax(&a.acc[VC_MAXV], (unsigned long long)mv_);
+            if (mh_) atomicMax(&a.acc[VC_MAXH], (unsigned long long)mh_);
+        }
+    }
+    if (cb == 0 && tid == 0 && n_obs) atomicAdd(&a.acc[VC_OBS], (unsigned long long)n_obs);
+    if (tid < npc && p_reach) atomicAdd(&a.acc[VC_REACH + p_i], (unsigned long long)p_reach);
+    __syncthreads();
+    for (uint32_t i = tid; i < 2u * GS_VC_BUCKETS; i += LB) {
+        const uint32_t c = (&s_hist[0][0])[i];
+        if (c) atomicAdd(&a.acc[VC_VH + i], (unsigned long long)c);
+    }
+    if (a.rows)
+        for (uint32_t i = tid; i < nrow; i += LB)
+            if (s_rows[i]) atomicAdd(&a.rows[o0 + i], s_rows[i]);
+}
+
 // Escaped owner columns (gs_config.esc_cols), after a lag sweep: one workgroup decides the moves -- an escaped
 // column none of whose views is hot any more (every lag < HOT_HB) goes back to 8-bit views, a column the sweep
 // flagged (a view lagging by >= 2^7) takes a free slot (none free: counted in err_hb_lag) -- and marks every
@@ -5385,6 +5738,8 @@ struct gs_handle {
     bool timing;
     uint32_t *heavy_buf = nullptr;  // k_pack_heavy's slot list (Dev::heavy): [0] = count, then up to N slot ids
     uint16_t *sm_buf = nullptr;     // Dev::sm (one-slice prefix-view handles)
+    unsigned long long *vc_buf = nullptr;  // gs_view_census scratch: VC_NUM u64 accumulators, then the probes
+    std::vector<uint64_t> vc_img;          // ... and its host image (the upload before, the read after the pass)
     hipStream_t hside = nullptr;    // k_pack_heavy's stream (forked after the lite slot work, joined after the packer)
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> tev[GS_KT_KINDS];
@@ -5979,6 +6334,7 @@ void gs_destroy(gs_handle *h) {
     if (h->grp) (void)hipFree(h->grp);
     if (h->heavy_buf) (void)hipFree(h->heavy_buf);
     if (h->sm_buf) (void)hipFree(h->sm_buf);
+    if (h->vc_buf) (void)hipFree(h->vc_buf);
     if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
     if (h->ev_join) (void)hipEventDestroy(h->ev_join);
     if (h->hside) (void)hipStreamDestroy(h->hside);
@@ -7053,6 +7409,71 @@ int gs_fd_census(gs_handle *h, const uint8_t *up, gs_census *out) {
     out->up_live = acc[2];
     out->down_pairs = acc[3];
     out->down_live = acc[4];
+    return GS_OK;
+}
+
+static_assert(sizeof(gs_view_totals) == 56 * 8, "gs_view_totals layout");
+static_assert(sizeof(gs_probe) == 8, "gs_probe layout");
+
+int gs_view_census(gs_handle *h, const uint8_t *up, uint32_t flags, const gs_probe *probes, uint32_t n_probes,
+                   uint64_t *reach, uint32_t *owners, uint32_t *rows, gs_view_totals *out) {
+    if (!h) return GS_E_INVALID;
+    if (!out) return fail(h, GS_E_INVALID, "gs_view_census: out is NULL");
+    if (flags & ~GS_VC_HEARTBEATS) return fail(h, GS_E_INVALID, "gs_view_census: unknown flags 0x%x", flags);
+    if (n_probes > GS_VC_MAX_PROBES) return fail(h, GS_E_INVALID, "gs_view_census: %u probes (at most %u)", n_probes, GS_VC_MAX_PROBES);
+    if (n_probes && (!probes || !reach)) return fail(h, GS_E_INVALID, "gs_view_census: probes without their arrays");
+    for (uint32_t i = 0; i < n_probes; i++)
+        if (probes[i].owner >= h->N) return fail(h, GS_E_INVALID, "gs_view_census: probe %u owner %u >= %u nodes", i, probes[i].owner, h->N);
+    if (!h->booted) return fail(h, GS_E_INVALID, "gs_view_census: not booted");
+    constexpr size_t WORDS = VC_NUM + GS_VC_MAX_PROBES;  // u64 accumulators, then {column, version} per probe
+    if (!h->vc_buf) HIPCHK(h, hipMalloc(&h->vc_buf, WORDS * 8));
+    h->vc_img.assign(WORDS, 0ull);
+    for (uint32_t i = 0; i < n_probes; i++) {
+        const uint32_t j = probes[i].owner;  // a probe of another slice's owner reaches nobody here
+        const uint32_t c = j >= h->col_lo && j - h->col_lo < h->ncol ? j - h->col_lo : NONE;
+        h->vc_img[VC_NUM + i] = (uint64_t)c | (uint64_t)probes[i].version << 32;
+    }
+    hipStream_t s = h->stream;
+    HIPCHK(h, hipMemcpyAsync(h->vc_buf, h->vc_img.data(), WORDS * 8, hipMemcpyHostToDevice, s));
+    if (owners) HIPCHK(h, hipMemsetAsync(owners, 0, (size_t)3 * h->ncol * 4, s));
+    if (rows) HIPCHK(h, hipMemsetAsync(rows, 0, (size_t)h->N * 4, s));
+    VcArgs a;
+    a.up = up;
+    a.flags = flags;
+    a.n_probes = n_probes;
+    a.acc = h->vc_buf;
+    a.probes = reinterpret_cast<const uint32_t *>(h->vc_buf + VC_NUM);
+    a.owners = owners;
+    a.rows = rows;
+    const Dev &d = h->d;
+    const bool swar = (d.flags & GS_CANONICAL) && d.hb8 && d.mv8 && d.self_pk;
+    const uint32_t per = swar ? 16u : 8u, chunks = (h->ncol + LB * per - 1) / (LB * per);
+    const uint32_t grid = (h->N + VC_BAND - 1) / VC_BAND * chunks;
+    if (swar)
+        k_view_census<true><<<grid, LB, 0, s>>>(d, a, chunks);
+    else
+        k_view_census<false><<<grid, LB, 0, s>>>(d, a, chunks);
+    HIPCHK(h, hipGetLastError());
+    HIPCHK(h, hipMemcpyAsync(h->vc_img.data(), h->vc_buf, (size_t)VC_NUM * 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipStreamSynchronize(s));
+    const uint64_t *acc = h->vc_img.data();
+    memset(out, 0, sizeof *out);
+    out->observers = acc[VC_OBS];
+    out->views = acc[VC_VIEWS];
+    out->unknown = acc[VC_UNK];
+    out->behind = acc[VC_BEHIND];
+    out->inexact = acc[VC_INEX];
+    out->max_version_lag = acc[VC_MAXV];
+    out->max_heartbeat_lag = acc[VC_MAXH];
+    // the kernel counts the non-zero lags: bucket 0 is the rest of the known views
+    uint64_t nzv = 0, nzh = 0;
+    for (uint32_t b = 1; b < GS_VC_BUCKETS; b++) {
+        nzv += out->version_lag_hist[b] = acc[VC_VH + b];
+        nzh += out->heartbeat_lag_hist[b] = acc[VC_HH + b];
+    }
+    out->version_lag_hist[0] = out->views - nzv;
+    if (flags & GS_VC_HEARTBEATS) out->heartbeat_lag_hist[0] = out->views - nzh;
+    for (uint32_t i = 0; i < n_probes; i++) reach[i] = acc[VC_REACH + i];
     return GS_OK;
 }
 

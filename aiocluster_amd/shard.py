@@ -200,6 +200,11 @@ def run_sliced_phase(slices, comm, mtu: int, t: int, ini, res, cache: dict | Non
     return steps
 
 
+def _slice_block(n: int, world: int) -> int:
+    """Owner columns of every slice but the last (gs_config.n_shards: ceil(N / G) rounded up to 64)."""
+    return n if world <= 1 else (-(-n // world) + 63) // 64 * 64
+
+
 class ShardGroup:
     """The owner-column slices of one simulated cluster, driven like one ``GossipSim``."""
 
@@ -336,6 +341,60 @@ class ShardGroup:
             self.comm.dist.all_reduce(v, group=self.comm.group)
             local = dict(zip(CENSUS_FIELDS, (int(x) for x in v.tolist())))
         return local
+
+    def view_census(self, up=None, heartbeats: bool = False, probes=(), per_owner: bool = False,
+                    per_row: bool = False) -> dict:
+        """``GossipSim.view_census`` of the whole cluster: totals, histograms, ``reach`` and ``row_stale`` summed
+        over the slices (``observers`` taken once), maxima maxed, the per-owner tensors joined along the owner
+        axis.  Over a ``DistComm`` the sums and maxima are all-reduced as ``fd_census`` does and the per-owner
+        parts gathered through the comm (every rank gets the whole result)."""
+        import torch
+
+        from ._lib import VIEW_HIST_FIELDS, VIEW_MAX_FIELDS, VIEW_TOTAL_FIELDS
+
+        probes = list(probes)
+        parts = [s.view_census(up, heartbeats, probes, per_owner, per_row) for s in self.slices]
+        sums = [k for k in VIEW_TOTAL_FIELDS if k not in VIEW_MAX_FIELDS and k != "observers"]
+        vec = [sum(p[k] for p in parts) for k in sums]
+        for k in VIEW_HIST_FIELDS:
+            vec += [sum(p[k][b] for p in parts) for b in range(len(parts[0][k]))]
+        vec += [sum(p["reach"][i] for p in parts) for i in range(len(probes))]
+        mx = [max(p[k] for p in parts) for k in VIEW_MAX_FIELDS]
+        dist = isinstance(self.comm, DistComm)
+        dev = self.slices[0].device
+        if dist:
+            d = self.comm.dist
+            cdev = "cpu" if d.get_backend(self.comm.group) == "gloo" else dev
+            v = torch.tensor(vec, dtype=torch.int64, device=cdev)
+            m = torch.tensor(mx, dtype=torch.int64, device=cdev)
+            d.all_reduce(v, group=self.comm.group)
+            d.all_reduce(m, op=d.ReduceOp.MAX, group=self.comm.group)
+            vec, mx = [int(x) for x in v.tolist()], [int(x) for x in m.tolist()]
+        out = {"observers": parts[0]["observers"]}
+        it = iter(vec)
+        out.update((k, next(it)) for k in sums)
+        out.update(zip(VIEW_MAX_FIELDS, mx))
+        out = {k: out[k] for k in VIEW_TOTAL_FIELDS}
+        for k in VIEW_HIST_FIELDS:
+            out[k] = [next(it) for _ in parts[0][k]]
+        out["converged"] = out["behind"] == 0 and out["unknown"] == 0
+        out["reach"] = [next(it) for _ in probes]
+        if per_owner:
+            for k in ("owner_behind", "owner_unknown", "owner_max_lag"):
+                t = torch.cat([p[k] for p in parts])
+                if dist:  # slices differ in width (the last one is shorter): gathered padded to the widest
+                    blk = _slice_block(self.n, self.comm.world)
+                    pad = torch.zeros(blk, dtype=t.dtype, device=t.device)
+                    pad[: t.numel()] = t
+                    allp = self.comm.gather([pad])
+                    t = torch.cat([allp[g, : min(blk, self.n - g * blk)] for g in range(self.comm.world)])
+                out[k] = t
+        if per_row:
+            t = torch.stack([p["row_stale"] for p in parts]).sum(0, dtype=torch.int32)
+            if dist:
+                t = self.comm.gather([t]).sum(0, dtype=torch.int32)
+            out["row_stale"] = t
+        return out
 
     def export(self) -> dict:
         """The slices this process holds, joined along the owner axis (all of them in-process)."""

@@ -551,6 +551,57 @@ class GossipSim:
         self._chk(self.L.gs_fd_census(self.h, C.c_void_p(u.data_ptr()), C.byref(c)), "gs_fd_census")
         return {n: int(getattr(c, n)) for n in _lib.CENSUS_FIELDS}
 
+    def view_census(self, up=None, heartbeats: bool = False, probes=(), per_owner: bool = False,
+                    per_row: bool = False) -> dict:
+        """gs_view_census: how far the data has spread, in one read-only device pass (blocking).  Over the
+        observer rows with ``up[o] != 0`` (default: all) and this handle's owner columns: ``observers``,
+        ``views`` (known pairs), ``unknown``, ``behind`` (views whose max_version is below the owner's own),
+        ``inexact`` (views with holes), ``max_version_lag``, ``version_lag_hist`` (20 buckets: lag 0, then
+        2^(b-1) <= lag < 2^b) and, with ``heartbeats``, ``max_heartbeat_lag`` / ``heartbeat_lag_hist``;
+        ``converged`` = nothing behind and nothing unknown; ``reach[i]`` = the counted observers whose view of
+        ``probes[i] = (owner, version)`` has max_version >= version (at most 64 probes).  ``per_owner`` adds the
+        device int32 tensors ``owner_behind``, ``owner_unknown``, ``owner_max_lag`` ([ncol]); ``per_row`` adds
+        ``row_stale`` ([N]: the owner columns each counted observer is behind on or does not know)."""
+        self._flush()
+        torch = self.torch
+        u = None
+        if up is not None:
+            u = up if hasattr(up, "data_ptr") else self._dev(np.asarray(up, dtype=np.uint8), torch.uint8)
+        probes = [(int(j), int(v)) for j, v in probes]
+        n = len(probes)
+        pr = (_lib.GsProbe * max(n, 1))(*[_lib.GsProbe(j, v) for j, v in probes])
+        reach = (C.c_uint64 * max(n, 1))()
+        owners = torch.empty((3, self.ncol), dtype=torch.int32, device=self.device) if per_owner else None
+        rows = torch.empty(self.n, dtype=torch.int32, device=self.device) if per_row else None
+        tot = _lib.GsViewTotals()
+        self._chk(self.L.gs_view_census(self.h, C.c_void_p(u.data_ptr()) if u is not None else None,
+                                        _lib.GS_VC_HEARTBEATS if heartbeats else 0, pr if n else None, n,
+                                        reach if n else None,
+                                        C.c_void_p(owners.data_ptr()) if per_owner else None,
+                                        C.c_void_p(rows.data_ptr()) if per_row else None, C.byref(tot)),
+                  "gs_view_census")
+        out = {k: int(getattr(tot, k)) for k in _lib.VIEW_TOTAL_FIELDS}
+        for k in _lib.VIEW_HIST_FIELDS:
+            out[k] = [int(x) for x in getattr(tot, k)]
+        out["converged"] = out["behind"] == 0 and out["unknown"] == 0
+        out["reach"] = [int(reach[i]) for i in range(n)]
+        if per_owner:
+            out["owner_behind"], out["owner_unknown"], out["owner_max_lag"] = owners[0], owners[1], owners[2]
+        if per_row:
+            out["row_stale"] = rows
+        return out
+
+    def reach(self, owner: int, version: int | None = None, up=None) -> int:
+        """The observers (with ``up[o] != 0``; default all) whose view of ``owner`` has reached ``version``
+        (default: the owner's current max_version, i.e. its latest write)."""
+        self._flush()
+        if version is None:
+            jl = int(owner) - self.col_lo
+            if not 0 <= jl < self.ncol:
+                raise GsError(f"owner {owner} is not one of this slice's columns: pass its version")
+            version = int(self.region("SELF_MV", self.torch.int32, (self.np_,))[jl].item())
+        return self.view_census(up=up, probes=[(owner, version)])["reach"][0]
+
     def materialize_held(self, row_lo: int = 0, row_hi: int | None = None):
         """Write out GS_R_HELD for the prefix views of rows [row_lo, row_hi) (readback only)."""
         hi = self.n if row_hi is None else row_hi

@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define GS_API_VERSION 20
+#define GS_API_VERSION 21
 #define GS_MAX_PHASES 64  /* report bit planes' phases per plane base window of the scheduler (busy bits) */
 /* gs_schedule_phases: phases of one round's schedule.  Every selected exchange runs (server.py:476-493): phases
  * past the workload's tick budget are sub-phases, run at one tick (gs_run_phase at the previous phase's tick). */
@@ -456,6 +456,38 @@ int gs_schedule_phases(gs_handle *h, const uint8_t *up, uint32_t fanout, const i
 /* FailureDetector.live_nodes / dead_nodes of every up observer (failure_detector.py:63-67) counted
  * against the DEVICE up mask; blocking.  Sliced handles count their own target columns. */
 int gs_fd_census(gs_handle *h, const uint8_t *up, gs_census *out);
+
+/* Dissemination census: how far the data has spread.  One read-only streaming pass over GS_R_MV (and GS_R_HB with
+ * GS_VC_HEARTBEATS) over the observer rows with up[o] != 0 (DEVICE u8 array; NULL: all N rows) and this handle's
+ * owner columns.  A view's version lag is the owner's own max_version (GS_R_SELF_MV) minus the view's; its
+ * heartbeat lag the owner's own heartbeat minus the view's decoded heartbeat (escaped columns read from
+ * GS_R_ESC16).  reach[i] (HOST) = the counted observers that know probes[i].owner and whose view of it has
+ * max_version >= probes[i].version (the owner's own row counts; an owner outside this handle's columns gives 0;
+ * duplicates allowed).  Optional DEVICE outputs: owners[3][n_cols] = per owner column {views behind, observers that
+ * do not know it, largest version lag}; rows[N] = per observer the owner columns of this handle it is behind on or
+ * does not know (0 for rows not counted).  Blocking; every output is overwritten; no region and no field of
+ * gs_read_counters changes.  Sliced handles count their own columns: sums add over the slices (observers is the same
+ * in each), maxima take the largest.  GS_E_INVALID (checked before any device work): n_probes > GS_VC_MAX_PROBES, a
+ * probe owner >= N, out == NULL, unknown flag bits, n_probes > 0 with probes or reach NULL. */
+#define GS_VC_HEARTBEATS 1u   /* also read GS_R_HB: heartbeat-lag histogram and maximum */
+#define GS_VC_MAX_PROBES 64u
+#define GS_VC_BUCKETS 20u     /* bucket 0: lag 0; bucket b >= 1: 2^(b-1) <= lag < 2^b; bucket 19 also takes lag >= 2^19 */
+typedef struct gs_probe { uint32_t owner; uint32_t version; } gs_probe;   /* owner: global node index */
+typedef struct gs_view_totals {            /* all u64 */
+    uint64_t observers;        /* rows counted (up[o] != 0; up == NULL: all N) */
+    uint64_t views;            /* counted (observer, owner) pairs the observer knows, diagonal included */
+    uint64_t unknown;          /* counted pairs the observer does not know (general layout: GS_R_POS == GS_NONE; 0 in canonical) */
+    uint64_t behind;           /* known views with max_version < the owner's own (GS_R_SELF_MV) */
+    uint64_t inexact;          /* known views with GS_MV_INEXACT set (holes) */
+    uint64_t max_version_lag, max_heartbeat_lag;
+    uint64_t version_lag_hist[GS_VC_BUCKETS], heartbeat_lag_hist[GS_VC_BUCKETS];   /* over known views; each sums to `views` (heartbeat: only with GS_VC_HEARTBEATS, else zeros) */
+    uint64_t reserved[9];
+} gs_view_totals;
+int gs_view_census(gs_handle *h, const uint8_t *up /*DEVICE or NULL*/, uint32_t flags,
+                   const gs_probe *probes /*HOST*/, uint32_t n_probes, uint64_t *reach /*HOST [n_probes]*/,
+                   uint32_t *owners /*DEVICE [3][ncol] or NULL: behind, unknown, max version lag per owner column of this handle*/,
+                   uint32_t *rows /*DEVICE [N] or NULL: per observer, this handle's owner columns it is behind on or does not know; 0 for rows not counted*/,
+                   gs_view_totals *out /*HOST*/);
 
 /* Wire-format emitter: the protobuf bytes the reference's SerializeToString gives, from device state,
  * so a simulated cluster can talk to real aiocluster nodes (messages.proto:46-74).  String tables are

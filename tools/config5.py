@@ -8,8 +8,9 @@ of the nodes write one key and 1 % of those writes are deletes; tombstone grace 
 
 Per round it reports the failure detector's census (gs_fd_census: false-positive rate = pairs whose
 target is up but in the observer's dead set / pairs whose target is up, observer != target) and
-the round's counters (NodeDeltas, truncated NodeDeltas, tombstones collected), and at the end
-whether the version matrix converged (every view's max_version = the owner's).
+the round's counters (NodeDeltas, truncated NodeDeltas, tombstones collected) and dissemination census
+(gs_view_census: views behind their owner, views with holes, the largest version lag), and at the end
+whether the version matrix converged (every view's max_version = the owner's: no view behind).
 
 Usage: python tools/config5.py [--nodes 16384] [--warm 10] [--partition 30] [--heal 30] [--out f.json]
 """
@@ -76,19 +77,20 @@ def main():
         busy += dt
         exch += rd["exchanges"]
         cen = sim.fd_census(rd["up"])
+        vc = sim.view_census()
         c = sim.check()
         d = {k: c[k] - prev[k] for k in ("exchanges", "node_deltas", "truncated", "tomb_gc", "delta_bytes",
                                           "hb_reports")}
         prev = c
         stage = "warm" if r < args.warm else "partition" if r < args.warm + args.partition else "heal"
         fp = cen["up_dead"] / max(1, cen["up_pairs"])
-        per_round.append({"round": r, "stage": stage, "ms": dt * 1e3, "fp_rate": fp, **cen, **d})
+        per_round.append({"round": r, "stage": stage, "ms": dt * 1e3, "fp_rate": fp, **cen, **d,
+                          "behind": vc["behind"], "inexact": vc["inexact"], "max_version_lag": vc["max_version_lag"]})
         print(f"r{r:3d} {stage:9s} {dt * 1e3:7.1f} ms  fp {fp:.4f}  nd {d['node_deltas']}  trunc {d['truncated']}"
               f"  tombgc {d['tomb_gc']}", file=sys.stderr, flush=True)
     # version-matrix convergence: every observer's max_version of every owner = the owner's own
-    mv = sim.max_versions()[:, :n]
-    own = torch.diagonal(mv).clone()
-    lag_views = int((mv != own[None, :]).sum().item())
+    vc = sim.view_census()
+    lag_views = vc["behind"] + vc["unknown"]
     part = [x for x in per_round if x["stage"] == "partition"]
     heal = [x for x in per_round if x["stage"] == "heal"]
     out = {
@@ -105,6 +107,7 @@ def main():
         "truncated_total": sum(x["truncated"] for x in per_round),
         "tomb_gc_total": sum(x["tomb_gc"] for x in per_round),
         "views_lagging_at_end": lag_views,
+        "converged": vc["converged"],
         "rounds": per_round,
     }
     s = json.dumps(out, indent=1)
