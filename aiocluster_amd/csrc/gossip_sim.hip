@@ -1990,45 +1990,115 @@ __device__ __forceinline__ uint32_t wave_scan_dpp(uint32_t x) {
     return x;
 }
 
-// One direction's stale owners of one step (nm[q]: bit 7 of byte i = column c + 4 q + i) go out as records
-// {column, sender max_version byte | receiver max_version byte << 16} appended in column order (lane order,
-// then column) to the wave's list L (the first GS_CAND_CAP; cnt counts all), and -- from the step whose owners
-// overflow the list on -- as natural-order bitmap bits, 16 per lane (the packers walk the bitmap past the
-// last record).  Every lane of the wave calls this (act = false: no columns).  The bytes are decoded into
+// A direction's stale owners of one step (mask words: bit 7 of byte i of word q = column c + 4 q + i) go out as
+// records {column, sender max_version byte | receiver max_version byte << 16} appended in column order (lane
+// order, then column) to the wave's list (the first GS_CAND_CAP; the count counts all), and -- from the step whose
+// owners overflow the list on -- as natural-order bitmap bits, 16 per lane (the packers walk the bitmap past the
+// last record).  Every lane of the wave calls emit_v (act = false: no columns).  The bytes are decoded into
 // the record's word form after the loop (p1v_decode_records): a load of the owner's own max_version here
 // would make the wave wait for the loads in flight for the next step.
-__device__ __forceinline__ void emit_v(uint16_t *gw16, uint2 *L, uint32_t &cnt, uint32_t c, bool act,
-                                       const uint32_t (&nm)[4], const uint4 &sS, const uint4 &sR, uint32_t &alg,
-                                       uint32_t (&rec)[4]) {
-    const uint32_t my = act ? (uint32_t)(__popc(nm[0]) + __popc(nm[1]) + __popc(nm[2]) + __popc(nm[3])) : 0u;
-    const uint32_t incl = wave_scan_dpp(my);
-    const uint32_t tot = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
-    if (act && cnt + tot > GS_CAND_CAP) {
-        gw16[c >> 4] = (uint16_t)(nib7(nm[0]) | (nib7(nm[1]) << 4) | (nib7(nm[2]) << 8) | (nib7(nm[3]) << 12));
-        alg += 2;
-    }
-    if (tot == 0u) return;
-    if (my) {
-        uint32_t off = cnt + incl - my;
-        const uint32_t s4[4] = {sS.x, sS.y, sS.z, sS.w}, r4[4] = {sR.x, sR.y, sR.z, sR.w};
-        // straight-line (at most 16 records): a loop with stores would make the compiler wait for every load
-        // in flight before entering it (the loaded views it reads were loaded outside it)
+//
+// The work follows the records, not the columns (a step of 1024 columns has about 9 stale owners a direction):
+// each lane packs its 16 flags into one mask in column order, one wave scan ranks both directions' counts
+// (lo half b -> a, hi half a -> b: a lane has at most 16, a wave at most 1024), and the records go out level
+// by level -- level r stores the r-th stale owner of every lane that has one, and the step's levels end at the
+// first one no lane needs.
+
+// bit 7 of byte i of w[q] (w holds no other bits) -> bit 4 q + i: one lane's 16 columns in column order
+__device__ __forceinline__ uint32_t mask16(const uint32_t (&w)[4]) {
+    uint32_t z = (w[0] >> 7) | (w[1] >> 3), y = (w[2] >> 7) | (w[3] >> 3);  // byte i: bit 0 = word q, bit 4 = q + 1
+    z |= z >> 7;
+    y |= y >> 7;
+    z |= z >> 14;
+    y |= y >> 14;
+    return (z & 0xFFu) | ((y & 0xFFu) << 8);
+}
+// the inverse for one nibble pair: bit 4 q + i of m -> bit 7 of byte i (q = 0 .. 3)
+__device__ __forceinline__ void unmask16(uint32_t m, uint32_t (&w)[4]) {
 #pragma unroll
-        for (int q = 0; q < 4; q++) {
-#pragma unroll
-            for (int i = 0; i < 4; i++) {
-                if ((nm[q] >> (8 * i + 7)) & 1u) {
-                    if (off < GS_CAND_CAP) {
-                        L[off] = make_uint2(c + 4u * q + i, ((s4[q] >> (8 * i)) & 0xFFu) | (((r4[q] >> (8 * i)) & 0xFFu) << 16));
-                        rec[q] |= 0x80u << (8 * i);
-                        alg += 8;
-                    }
-                    off++;
-                }
-            }
+    for (int q = 0; q < 4; q++) w[q] = spread7((m >> (4 * q)) & 0xFu);
+}
+
+// One direction's records of one step: the lane's stale owners m (mask16 order) go to p[0], p[1], ... (p: the
+// lane's first slot in the list), the first lim of them (the list's room); m keeps the owners not recorded.
+// Level R runs inside level R - 1's lanes (a lane with an R-th record has an (R - 1)-th), so each level is
+// one exec mask and one branch that skips the rest once no lane has a record left; the nest is cut into
+// four of four levels, each under a wave-uniform test (a nest of 16 would hold 16 saved exec masks in
+// SGPRs).  Straight-line, forward branches only: a loop with stores would make the compiler wait for every
+// load in flight before entering it (the loaded views it reads were loaded outside it).
+template <int R, int END>
+__device__ __forceinline__ void emit_nest(uint2 *p, uint32_t lim, uint32_t &m, uint32_t c, const uint4 &sS,
+                                          const uint4 &sR) {
+    if constexpr (R < END) {
+        if (m != 0u && (uint32_t)R < lim) {
+            const uint32_t k = (uint32_t)__builtin_ctz(m);  // the column: word k >> 2, byte k & 3
+            m &= m - 1u;
+            // v_perm: selector 0-3 = a byte of the second operand, 4-7 = of the first, 0x0c = zero.  The byte
+            // comes from words 0-1 or from words 2-3: the other pair's selector is all zero bytes (no select
+            // between the loaded words themselves: the compiler would index them in scratch memory)
+            const bool up = (k & 8u) != 0u;
+            const uint32_t kl = up ? 0x0Cu : k, kh = up ? (k & 7u) : 0x0Cu;
+            const uint32_t ms = __builtin_amdgcn_perm(sS.y, sS.x, 0x0C0C0C00u | kl) |
+                                __builtin_amdgcn_perm(sS.w, sS.z, 0x0C0C0C00u | kh);
+            const uint32_t mr = __builtin_amdgcn_perm(sR.y, sR.x, 0x0C000C0Cu | (kl << 16)) |
+                                __builtin_amdgcn_perm(sR.w, sR.z, 0x0C000C0Cu | (kh << 16));
+            p[R] = make_uint2(c + k, ms | mr);
+            emit_nest<R + 1, END>(p, lim, m, c, sS, sR);
         }
     }
-    cnt += tot;
+}
+template <int R>
+__device__ __forceinline__ void emit_levels(uint2 *p, uint32_t lim, uint32_t &m, uint32_t c, const uint4 &sS,
+                                            const uint4 &sR) {
+    if constexpr (R < 16) {
+        if (R == 0 || __builtin_amdgcn_ballot_w64(m != 0u && (uint32_t)R < lim) != 0ull) {  // wave-uniform
+            emit_nest<R, R + 4>(p, lim, m, c, sS, sR);
+            emit_levels<R + 4>(p, lim, m, c, sS, sR);
+        }
+    }
+}
+
+// Both directions of one step (b -> a: nba, list LBA, sender b; a -> b: nab, LAB, sender a); rBA / rAB: the
+// recorded owners (bit 7 of byte i), which the speculative merge reads.  The masks of a lane without columns
+// (act = false) are zero.
+__device__ __forceinline__ void emit_v(uint16_t *gBA, uint16_t *gAB, uint2 *LBA, uint2 *LAB, uint32_t &nBA,
+                                       uint32_t &nAB, uint32_t c, bool act, const uint32_t (&nba)[4],
+                                       const uint32_t (&nab)[4], const uint4 &mA, const uint4 &mB, uint32_t &alg,
+                                       uint32_t (&rBA)[4], uint32_t (&rAB)[4]) {
+    const uint32_t m0 = mask16(nba), m1 = mask16(nab);
+    const uint32_t my = (uint32_t)__popc(m0) | ((uint32_t)__popc(m1) << 16);
+    const uint32_t incl = wave_scan_dpp(my);  // (both halves at once: no carry out of the low one)
+    const uint32_t tot = (uint32_t)__builtin_amdgcn_readlane((int)incl, 63);
+    const uint32_t t0 = tot & 0xFFFFu, t1 = tot >> 16, excl = incl - my;
+    const bool ov0 = nBA + t0 > GS_CAND_CAP, ov1 = nAB + t1 > GS_CAND_CAP;  // wave-uniform
+    if (act && ov0) {  // (a step without stale owners too, once the list has overflowed)
+        gBA[c >> 4] = (uint16_t)m0;
+        alg += 2;
+    }
+    if (act && ov1) {
+        gAB[c >> 4] = (uint16_t)m1;
+        alg += 2;
+    }
+    // (few values live across the levels: the loop runs at the register limit of its occupancy)
+    alg += 8u * ((my & 0xFFFFu) + (my >> 16));
+    const uint32_t o0 = nBA + (excl & 0xFFFFu), o1 = nAB + (excl >> 16);
+    uint32_t u0 = m0, u1 = m1;  // the owners not recorded yet
+    emit_levels<0>(LBA + o0, GS_CAND_CAP - min(o0, GS_CAND_CAP), u0, c, mB, mA);
+    emit_levels<0>(LAB + o1, GS_CAND_CAP - min(o1, GS_CAND_CAP), u1, c, mA, mB);
+    if (ov0 || ov1) {  // a list filled up in this step or before: the owners left in u0 / u1 are not recorded
+        // (the masks are packed again here, in the rare branch, so that m0 / m1 are not live across the levels)
+        unmask16(mask16(nba) ^ u0, rBA);
+        unmask16(mask16(nab) ^ u1, rAB);
+        alg -= 8u * (uint32_t)(__popc(u0) + __popc(u1));
+    } else {
+#pragma unroll
+        for (int q = 0; q < 4; q++) {
+            rBA[q] = nba[q];
+            rAB[q] = nab[q];
+        }
+    }
+    nBA += t0;
+    nAB += t1;
 }
 
 // k_pass1v's per-column path for one lane's 16 columns (out of line: it runs for a few lanes per exchange, and
@@ -2498,8 +2568,7 @@ __global__ __launch_bounds__(XB, P1V_WAVES) void k_pass1v(Dev d, const int32_t *
                 alg += 4;
             }
             uint32_t rBA[4] = {0u, 0u, 0u, 0u}, rAB[4] = {0u, 0u, 0u, 0u};  // recorded stale owners
-            emit_v(gBA, LBA, nBAc, c, act, nba, v.mB, v.mA, alg, rBA);  // b -> a: sender b, receiver a
-            emit_v(gAB, LAB, nABc, c, act, nab, v.mA, v.mB, alg, rAB);
+            emit_v(gBA, gAB, LBA, LAB, nBAc, nABc, c, act, nba, nab, v.mA, v.mB, alg, rBA, rAB);
             if (spec && act) {
                 // speculative merge (Dev::spec): each recorded stale owner whose two views are prefix views
                 // (GS_MV_INEXACT clear: bit 7 of both bytes) gets the sender's view now, in the 16 bytes this
