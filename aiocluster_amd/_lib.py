@@ -90,7 +90,7 @@ EXPORTS = [
     "gs_latest_tick", "gs_flush_reports", "gs_set_ring_rows", "gs_mark", "gs_view_census",
 ]
 
-API_VERSION = 21
+API_VERSION = 22
 MAX_PHASES = 64  # GS_MAX_PHASES
 MAX_SCHED_PHASES = 65536  # GS_MAX_SCHED_PHASES
 

@@ -173,10 +173,11 @@ struct Dev {
     uint32_t *esc_slot, *esc_owner, *esc_req;
     uint32_t EC;
     // event stream (gs_set_events): records {observer, owner, key | kind << 8, old version, new version,
-    // tick, seq, 0}; kind 0 = on_key_change, 1 = node join, 2 = node leave; seq orders them (gossip_sim.h,
-// gs_set_events).  ev == nullptr: off
+    // tick, seq, phase}; kind 0 = on_key_change, 1 = node join, 2 = node leave; seq orders them, phase = ev_phase
+    // in apply_delta's records and 0 in every other (gossip_sim.h, gs_set_events).  ev == nullptr: off
     uint32_t *ev, *ev_count;
     uint32_t ev_cap;
+    uint32_t ev_phase;  // phases started on this handle since gs_set_events, this one included (1 = the first)
     // the exact packer's heavy slots (round 6): k_pack_slice lists a slot with more than heavy_t stale owners here
     // ([0] = count, then slot ids) instead of walking it, and k_pack_heavy packs it with a workgroup of its own;
     // nullptr: no hand-off (set per launch by the host, one-slice record phases only)
@@ -293,14 +294,16 @@ __device__ inline void emit_event(const Dev &d, uint32_t o, uint32_t j, uint32_t
 }
 
 // on_key_change of apply_delta (state.py:228-231), out of line: the event path stays off the register
-// budget of the packing kernels.  seq = the sender's dict position of the owner (NodeDelta order).
+// budget of the packing kernels.  seq = the sender's dict position of the owner (NodeDelta order); phase = the
+// phase's ordinal (Dev::ev_phase), which tells the phases of one tick (sub-phases) apart.
 __device__ __noinline__ void emit_apply_event(uint32_t *ev, uint32_t *evc, uint32_t cap, const uint32_t *pos_s, uint32_t r,
-                                              uint32_t jg, uint32_t j, uint32_t q, uint32_t v_old, uint32_t v, uint32_t t) {
+                                              uint32_t jg, uint32_t j, uint32_t q, uint32_t v_old, uint32_t v, uint32_t t,
+                                              uint32_t phase) {
     const uint32_t i = atomicAdd(evc, 1u);
     if (i >= cap) return;
     uint4 *rec = reinterpret_cast<uint4 *>(ev + (size_t)i * 8);
     rec[0] = make_uint4(r, jg, q | (EV_KEY << 8), v_old);
-    rec[1] = make_uint4(v, t, pos_s ? pos_s[j] : jg, 0u);
+    rec[1] = make_uint4(v, t, pos_s ? pos_s[j] : jg, phase);
 }
 
 // ------------------------------------------------------------------ packing / apply
@@ -619,7 +622,7 @@ __device__ __forceinline__ void apply_cand(const Dev &d, uint32_t s, uint32_t r,
                 if (d.ev)
                     emit_apply_event(d.ev, d.ev_count, d.ev_cap, (d.flags & GS_CANONICAL) ? nullptr : d.pos + pix(d, s, 0),
                                      r, d.col_lo + c.j, c.j, (uint32_t)q, wr ? (uint32_t)d.hist[hix(d, c.j, wr, q)] : 0u,
-                                     v, t);
+                                     v, t, d.ev_phase);
                 wr = ws;
                 if (tt) { tsr[q] = st ? t : NONE; alg += 4; }
                 if (st) tomb = true;
@@ -6604,6 +6607,7 @@ int gs_run_phase(gs_handle *h, const int32_t *ini, const int32_t *res, uint32_t 
     const size_t lds = exchange_lds(h);
     const SliceIO io{};
     h->seq += 1;
+    h->d.ev_phase += 1;
     h->reports_pending = true;
     h->last_phase_tick = tick;
     h->hb_incs++;
@@ -6639,6 +6643,7 @@ int gs_phase_count(gs_handle *h, const int32_t *ini, const int32_t *res, uint32_
     SliceIO io{};
     io.tot = slice_bytes;
     h->seq += 1;
+    h->d.ev_phase += 1;
     h->reports_pending = true;
     h->last_phase_tick = tick;
     h->hb_incs++;
@@ -6915,6 +6920,7 @@ int group_steps(gs_handle *const *hs, uint32_t nh, const int32_t *ini, const int
         if ((rc = fd_age(h, tick)) || (rc = plane_slot(h, tick, h->sub_ok && tick == h->last_phase_tick))) return rc;
         h->sub_ok = true;
         h->seq += 1;
+        h->d.ev_phase += 1;
         h->reports_pending = true;
         h->last_phase_tick = tick;
         h->hb_incs++;
@@ -7368,6 +7374,7 @@ int gs_set_events(gs_handle *h, uint32_t *records, uint32_t capacity, uint32_t *
     h->d.ev_count = records ? count : nullptr;
     h->d.ev_cap = records ? capacity : 0u;
     h->d.ev_wseq = 0u;
+    h->d.ev_phase = 0u;
     return GS_OK;
 }
 

@@ -89,7 +89,7 @@ def run_phases(sims, rd, events=None, group=None, phases=None):
             if s_._ev is not None:  # hook events: order_events needs each phase's exchange order
                 if group is not None:
                     raise ValueError("hook events on a sliced cluster are not supported (drain per slice)")
-                s_._ev_phases[t] = (a.cpu().numpy().astype(np.int64), b.cpu().numpy().astype(np.int64))
+                s_._ev_note_phase(a, b)
         if events is not None:
             e0 = s0.torch.cuda.Event(enable_timing=True)
             e1 = s0.torch.cuda.Event(enable_timing=True)

@@ -86,8 +86,9 @@ def fd_state_word(st8: np.ndarray, tod: np.ndarray) -> np.ndarray:
 
 def order_events(ev: np.ndarray, n: int, phases: dict, wmap: list) -> np.ndarray:
     """Permutation putting device event records (uint32 [m, 8], gs_set_events) in the reference's order:
-    by tick; owner writes by call order (``wmap``: record seq -> call index); in a phase (``phases``:
-    tick -> (initiators, responders)) by exchange index, the initiator's apply (SynAck delta,
+    by tick; owner writes (phase word 0) by call order (``wmap``: record seq -> call index); phases by
+    their ordinal (the record's phase word: several phases may share a tick); in a phase (``phases``:
+    ordinal -> (initiators, responders)) by exchange index, the initiator's apply (SynAck delta,
     server.py:351-353) before the responder's (Ack delta, 372-376), then the NodeDelta order (seq = the
     sender's dict position, state.py:346-413), then kv version; join / leave by observer, joins first,
     then node (the reference iterates sets there, server.py:611-614)."""
@@ -96,26 +97,26 @@ def order_events(ev: np.ndarray, n: int, phases: dict, wmap: list) -> np.ndarray
     kind = (ev[:, 2] >> 8).astype(np.int64)
     seq = ev[:, 6].astype(np.int64)
     obs = ev[:, 0].astype(np.int64)
-    k1, k2, k3, k4 = (np.zeros(m, np.int64) for _ in range(4))
+    k0, k1, k2, k3, k4 = (np.zeros(m, np.int64) for _ in range(5))
     lv = kind != 0
     k1[lv], k2[lv], k3[lv] = obs[lv], kind[lv], ev[lv, 1]
     kc = ~lv
-    wm = np.asarray(wmap, dtype=np.int64)
-    for tick in np.unique(t[kc]).tolist():
-        sel = kc & (t == tick)
-        ph = phases.get(tick)
-        if ph is None:  # owner writes (a seq the map does not cover: after every mapped write, in seq order)
-            sq = seq[sel]
-            k1[sel] = np.where(sq < len(wm), wm[np.minimum(sq, len(wm) - 1)], len(wm) + sq) if len(wm) else sq
-            continue
-        a, b = (np.asarray(x, dtype=np.int64) for x in ph)
+    k0[kc] = ev[kc, 7]
+    wr = kc & (k0 == 0)  # owner writes (a seq the map does not cover: after every mapped write, in seq order)
+    if wr.any():
+        wm = np.asarray(wmap, dtype=np.int64)
+        sq = seq[wr]
+        k1[wr] = np.where(sq < len(wm), wm[np.minimum(sq, len(wm) - 1)], len(wm) + sq) if len(wm) else sq
+    for o in np.unique(k0[kc & ~wr]).tolist():
+        sel = kc & (k0 == o)
+        a, b = (np.asarray(x, dtype=np.int64) for x in phases[o])
         ex = np.full(n, -1, np.int64)
         side = np.zeros(n, np.int64)
         ex[a] = np.arange(len(a))
         ex[b] = np.arange(len(b))
         side[b] = 1
         k1[sel], k2[sel], k3[sel], k4[sel] = ex[obs[sel]], side[obs[sel]], seq[sel], ev[sel, 4]
-    return np.lexsort((k4, k3, k2, k1, t))
+    return np.lexsort((k4, k3, k2, k1, k0, t))
 
 
 def make_config(n: int, k: int, cfg: dict, flags: int, hist_cap: int, shards: int = 1,
@@ -267,6 +268,7 @@ class GossipSim:
         self._ev_phases: dict = {}
         self._ev_wmap: list[int] = []
         self._ev_writes = 0
+        self._ev_ord = 0
         self.last_tick = 0
         self.q9_events: list = []
         if initial_values:
@@ -389,7 +391,7 @@ class GossipSim:
         if n == 0:
             return
         if self._ev is not None:
-            self._ev_phases[t] = (ini.cpu().numpy().astype(np.int64), res.cpu().numpy().astype(np.int64))
+            self._ev_note_phase(ini, res)
         self._chk(self.L.gs_run_phase(self.h, C.c_void_p(ini.data_ptr()), C.c_void_p(res.data_ptr()), n, t),
                   "gs_run_phase")
 
@@ -505,11 +507,18 @@ class GossipSim:
         self._chk(self.L.gs_check_heartbeat_lag(self.h), "gs_check_heartbeat_lag")
 
     # --------------------------------------------------------------- hook events
+    def _ev_note_phase(self, ini, res):
+        """Before a phase launch with events on: keep its exchange order under the ordinal the device writes into
+        the phase's records (phases started since gs_set_events, this one included; gossip_sim.h)."""
+        self._ev_ord = (self._ev_ord + 1) & 0xFFFFFFFF
+        self._ev_phases[self._ev_ord] = (ini.cpu().numpy().astype(np.int64), res.cpu().numpy().astype(np.int64))
+
     def enable_events(self, capacity: int = 1 << 20):
         """gs_set_events: record on_key_change / on_node_join / on_node_leave (see drain_events)."""
         torch = self.torch
         self._ev = torch.empty((capacity, 8), dtype=torch.int32, device=self.device)
-        self._ev_phases = {}  # phase tick -> (initiators, responders): the exchange order of that phase
+        self._ev_phases = {}  # phase ordinal -> (initiators, responders): the exchange order of that phase
+        self._ev_ord = 0      # phases started since gs_set_events (the device's count: the records' phase word)
         self._ev_wmap = []    # owner-write seq -> index among the caller's writes since enable_events
         # writes queued before this call (not yet flushed) are the first ones of the new numbering
         self._pending = [(*w[:-1], i) for i, w in enumerate(self._pending)]
@@ -525,7 +534,7 @@ class GossipSim:
     def drain_events(self) -> np.ndarray:
         """The events since the last drain, uint32 [n, 6] = observer, owner (node index), key | kind << 8,
         old version (0 = none), new version, tick; in the reference's order (gossip_sim.h, gs_set_events):
-        by tick; owner writes in call order; within a phase by exchange (its index in the phase), the
+        by tick; owner writes in call order; phases in call order (sub-phases share a tick); within a phase by exchange (its index in the phase), the
         initiator's apply before the responder's, the NodeDelta order (sender's dict position), kv version;
         liveness by observer, joins before leaves, then node.  Raises if the buffer overflowed."""
         self.sync()

@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define GS_API_VERSION 21
+#define GS_API_VERSION 22
 #define GS_MAX_PHASES 64  /* report bit planes' phases per plane base window of the scheduler (busy bits) */
 /* gs_schedule_phases: phases of one round's schedule.  Every selected exchange runs (server.py:476-493): phases
  * past the workload's tick budget are sub-phases, run at one tick (gs_run_phase at the previous phase's tick). */
@@ -412,7 +412,7 @@ int gs_check_heartbeat_lag(gs_handle *h);
 
 /* Batched hook events (Cluster.on_key_change / on_node_join / on_node_leave, server.py:217-257).
  * When enabled, every kernel that changes what a hook reports appends 8 x u32 records
- * {observer, owner, key | kind << 8, old version (0 = none), new version, tick, seq, 0} to the DEVICE
+ * {observer, owner, key | kind << 8, old version (0 = none), new version, tick, seq, phase} to the DEVICE
  * array records[capacity][8], counting in the DEVICE u32 *count (records beyond capacity are dropped
  * but counted; the caller resets *count).  kind 0 = on_key_change: a kv stored by apply_delta
  * (state.py:228-231) or an owner set / set_with_ttl (owner deletes mutate the stored value in
@@ -424,9 +424,13 @@ int gs_check_heartbeat_lag(gs_handle *h);
  *   apply_delta:  the sender's dict position of the owner (the NodeDelta order of the delta,
  *                 state.py:346-413); a NodeDelta's kvs are applied in version order;
  *   join / leave: 0 (the reference iterates Python sets there: no order to reproduce).
- * So the reference's order (oracle/gen_events_fixture.py) is: by tick; owner writes by seq; in a
- * phase by exchange (its index in the phase), the initiator's apply (SynAck delta) before the
- * responder's (Ack delta), then seq, then new version; liveness by observer, joins before leaves,
+ * phase tells the phases of one tick (sub-phases) apart, which tick and seq cannot: in an apply_delta
+ * record it is the phase's ordinal, the number of phases (gs_run_phase / gs_phase_count /
+ * gs_run_phase_group calls with n > 0) started on the handle since gs_set_events, that phase included
+ * (1 = the first, wrapping at 2^32); it is 0 in every other record.
+ * So the reference's order (oracle/gen_events_fixture.py) is: by tick; owner writes by seq; phases by
+ * ordinal; in a phase by exchange (its index in the phase), the initiator's apply (SynAck delta) before
+ * the responder's (Ack delta), then seq, then new version; liveness by observer, joins before leaves,
  * then owner.  Exchanges between prefix views take the per-key apply path while enabled.
  * records = NULL: off. */
 int gs_set_events(gs_handle *h, uint32_t *records, uint32_t capacity, uint32_t *count);

@@ -26,7 +26,7 @@ from refharness import RefSim, dt_tick  # noqa: E402
 
 from aiocluster_amd.scenario import initial_by_owner, replay_round, scenario_node_ids  # noqa: E402
 
-NAMES = ["trunc8", "fdgc12", "simple3", "cold64"]
+NAMES = ["trunc8", "fdgc12", "simple3", "cold64", "subring24", "subfront40"]
 
 
 def canonical_liveness(events):

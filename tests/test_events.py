@@ -14,7 +14,7 @@ from oracle import OracleSim
 from aiocluster_amd.scenario import replay_round
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-NAMES = ["trunc8", "fdgc12", "simple3", "cold64"]
+NAMES = ["trunc8", "fdgc12", "simple3", "cold64", "subring24", "subfront40"]
 
 
 def golden_events(name):
@@ -66,14 +66,15 @@ def test_device_events_prefix_views():
 
 class _SeqRecorder:
     """Proxies an OracleSim and turns its (reference-ordered) events into device-format records
-    (gs_set_events: 8 words, seq as the device computes it) call by call."""
+    (gs_set_events: 8 words, seq and phase as the device computes them) call by call; ``phases`` is keyed the
+    way GossipSim keys its own: by the phase's ordinal since events were enabled (several phases may share a tick)."""
 
     def __init__(self, orc):
-        self.orc, self.recs, self.phases, self.writes = orc, [], {}, 0
+        self.orc, self.recs, self.phases, self.writes, self.ord = orc, [], {}, 0, 0
 
-    def _take(self, seq_of):
+    def _take(self, seq_of, phase=0):
         for e in self.orc.drain_events().astype(np.int64).tolist():
-            self.recs.append(e + [seq_of(e), 0])
+            self.recs.append(e + [seq_of(e), phase])
 
     def write(self, t, j, k, op, v):
         self.orc.write(t, j, k, op, v)
@@ -92,10 +93,13 @@ class _SeqRecorder:
 
     def run_phase(self, t, pairs):
         self.orc.run_phase(t, pairs)
+        if len(pairs) == 0:  # GossipSim.run_phase starts no phase for an empty matching
+            return
         peer = {}
         for a, b in pairs:
             peer[a], peer[b] = b, a
-        self.phases[t] = ([a for a, _ in pairs], [b for _, b in pairs])
+        self.ord += 1
+        self.phases[self.ord] = ([a for a, _ in pairs], [b for _, b in pairs])
         order = {}
 
         def seq(e):  # the sender's dict position of the owner
@@ -104,7 +108,7 @@ class _SeqRecorder:
                 order[s] = {j: q for q, j in enumerate(self.orc.order(s))}
             return order[s][e[1]]
 
-        self._take(seq)
+        self._take(seq, self.ord)
 
     def liveness(self, t, up, r):
         self.orc.liveness(t, up, r)
