@@ -649,9 +649,10 @@ __device__ __forceinline__ void apply_cand(const Dev &d, uint32_t s, uint32_t r,
         return;
     }
     uint32_t *hrp = reinterpret_cast<uint32_t *>(d.held + pr * d.KP);
+    const uint32_t kw = d.KP >> 2;  // the row has KP / 4 words: the words past them are the next view's
 #pragma unroll
     for (int q = 0; q < KW; q++)
-        if (keep_held && (hr[q] != hr0[q] || c.rx)) { hrp[q] = hr[q]; alg += 4; }
+        if ((uint32_t)q < kw && keep_held && (hr[q] != hr0[q] || c.rx)) { hrp[q] = hr[q]; alg += 4; }
     mv_put(d, pr, mvw);
     if (g != c.gr) d.gc[pr] = g;
     alg += 8;

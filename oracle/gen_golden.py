@@ -143,6 +143,31 @@ SCENARIOS = {
     # state of every round (ring windows of 5, max_interval 0.25 s), subfront40 hashes and the final state
     "subring24": subring24,
     "subfront40": subfront40,
+    # key counts other than 2 / 4 / 8 / 16 / 64: odd K (KP = round_up(K, 4) > K) and 17 <= K <= 63 (the 16-word key
+    # arrays with unused words), each with an mtu that cuts NodeDeltas; keys21w starts warm and has no deletes (the
+    # prefix-view layouts replay it)
+    "keys5": (
+        WorkloadSpec(n=10, k=5, fanout=2, seed=605, init="cold", write_frac=0.5, delete_frac=0.2, ttl_frac=0.1,
+                     down_frac=0.3, down_rounds=4),
+        30,
+        {"mtu": 300, "tombstone_grace_s": 3, "window": 5, "max_interval_s": 1.0, "initial_interval_s": 1.0,
+         "phi_threshold": 3.0},
+        True,
+    ),
+    "keys37": (
+        WorkloadSpec(n=10, k=37, fanout=2, seed=637, init="cold", write_frac=0.5, delete_frac=0.2, ttl_frac=0.1,
+                     down_frac=0.3, down_rounds=4),
+        30,
+        {"mtu": 620, "tombstone_grace_s": 3, "window": 5, "max_interval_s": 1.0, "initial_interval_s": 1.0,
+         "phi_threshold": 3.0},
+        True,
+    ),
+    "keys21w": (
+        WorkloadSpec(n=12, k=21, fanout=2, seed=621, init="warm", write_frac=0.5, down_frac=0.3, down_rounds=4),
+        30,
+        {"mtu": 460, "initial_interval_s": 1.0, "phi_threshold": 3.0},
+        True,
+    ),
 }
 FULL_STATES = {"subring24"}  # callables whose fixture stores every round's state
 

@@ -40,7 +40,9 @@ PLAN = {"trunc8": (None, 64), "sched16": (None, 48), "fdgc12": (None, 40), "simp
         # large values (tests/bigvalues.py): few cases, each delta up to the mtu.  bigsleep12's senders answer the
         # nodes that are away (a Syn built from the sleeper's state as it stands: nothing is mutated), so whole
         # NodeDeltas past 65,535 bytes and the mtu's cut are in the bytes
-        "bigval6": ([0, 1, 4, 10], 30), "bigsleep12": ([2, 4, 5], 6, True)}
+        "bigval6": ([0, 1, 4, 10], 30), "bigsleep12": ([2, 4, 5], 6, True),
+        # 5, 37 and 21 keys (odd K, and the 16-word key arrays partly used)
+        "keys5": (None, 24), "keys37": (None, 24), "keys21w": (None, 24)}
 
 
 def capture(name):

@@ -31,3 +31,14 @@ def warm_k16_esc() -> dict:
 
 
 WARM_K16_ESC_KW = dict(tombstones=False, fd_ring=False, hb8=True, mv8=True, esc_cols=4)
+
+
+def warm_k37() -> dict:
+    """96 nodes, 37 keys (10 of the kernels' 16 key words, the last one with a single key), warm, a binding mtu,
+    churn; run with canonical prefix views."""
+    spec = WorkloadSpec(n=96, k=37, fanout=3, seed=37, init="warm", write_frac=0.6, down_frac=0.08, down_rounds=3)
+    cfg = {"mtu": 700, "phi_threshold": 3.0, "initial_interval_s": 1.0}
+    return make_scenario("ev_warm_k37", spec, ROUNDS, cfg)
+
+
+WARM_K37_KW = dict(tombstones=False, fd_ring=False)

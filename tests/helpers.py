@@ -11,7 +11,8 @@ from aiocluster_amd.scenario import initial_by_owner, replay, scenario_node_ids,
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 SCENARIOS = ["simple3", "trunc8", "sched16", "fdgc12", "q9x10", "cold64", "warm128", "cold256",
              "bigval6", "bigsleep12",  # values up to 16,383 bytes, NodeDeltas past 64 KiB (tests/bigvalues.py)
-             "subring24", "subfront40"]  # 13-95 phases per round, several at one tick (tests/manyphases.py)
+             "subring24", "subfront40",  # 13-95 phases per round, several at one tick (tests/manyphases.py)
+             "keys5", "keys37", "keys21w"]  # 5, 37 and 21 keys: odd K, the 16-word key arrays partly used
 
 
 def load_scenario(name):

@@ -2,7 +2,7 @@
 tests/test_gpu_events_layouts.py relies on, so that case never passes because its input was tame."""
 
 import numpy as np
-from eventcases import cold_k64, warm_k16_esc
+from eventcases import cold_k64, warm_k16_esc, warm_k37
 from helpers import make_backend
 from oracle import OracleSim
 
@@ -32,6 +32,18 @@ def test_cold_k64_truncates_and_reports_keys_past_31():
     applied = (kind == 0) & (ev[:, 0] != ev[:, 1])  # apply_delta's records: the observer is not the owner
     assert (key[applied] >= 32).sum() > 100 and key[applied].max() == 63
     assert ((kind == 0) & (ev[:, 0] == ev[:, 1]) & (key >= 32)).any()  # owner writes too
+
+
+def test_warm_k37_truncates_and_reports_keys_up_to_36():
+    scen = warm_k37()
+    assert scen["k"] == 37 and scen["n"] == 96 and scen["init"] == "warm"
+    assert {op for rd in scen["rounds"] for _, _, op, _ in rd["writes"]} == {0}  # SET only: prefix views
+    ev, s = run(scen)
+    assert s["truncated"] > 0
+    kind, key = ev[:, 2] >> 8, ev[:, 2] & 0xFF
+    assert set(kind.tolist()) == {0, 1, 2}
+    applied = (kind == 0) & (ev[:, 0] != ev[:, 1])  # apply_delta's records: the observer is not the owner
+    assert (key[applied] >= 32).any() and key[applied].max() == 36
 
 
 def test_warm_k16_esc_truncates_with_churn():

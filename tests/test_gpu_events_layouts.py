@@ -3,9 +3,9 @@
 While events are on, a phase runs neither the speculative pass-1 merge nor k_lite nor the heavy-slot kernel nor the
 version-log evaluation, and every prefix view takes apply_cand's per-key path: a combination of kernels that no
 other test runs.  The scenarios of tests/manyphases.py (128 nodes, k = 8, 9 rounds: a binding mtu, candidate
-records, mid-round plane replays, sub-phases, churn) and of tests/eventcases.py (64 keys; 16 keys with escape
-slots) are replayed in lockstep with the oracle, whose event order tests/test_events.py pins to the reference's
-(sub-phases included): after every round the drained events must equal the oracle's as lists, in exact order, and
+records, mid-round plane replays, sub-phases, churn) and of tests/eventcases.py (64 keys; 37 keys in canonical
+prefix views; 16 keys with escape slots) are replayed in lockstep with the oracle, whose event order
+tests/test_events.py pins to the reference's (sub-phases included): after every round the drained events must equal the oracle's as lists, in exact order, and
 the whole export must be equal; at the end the counters.  Further cases turn events on and off between rounds,
 suppress the heavy-slot hand-off, and fill the record buffer past its capacity (a documented, bounds-checked drop).
 """
@@ -18,7 +18,7 @@ import sys
 
 import numpy as np
 import pytest
-from eventcases import COLD_K64_KW, WARM_K16_ESC_KW, cold_k64, warm_k16_esc
+from eventcases import COLD_K64_KW, WARM_K16_ESC_KW, WARM_K37_KW, cold_k64, warm_k16_esc, warm_k37
 from helpers import compare_exports, make_backend
 from manyphases import LAYOUTS, RING_ROWS, device_scenario
 from oracle import OracleSim
@@ -158,6 +158,15 @@ def test_events_with_64_keys_general_layout():
     ev = np.asarray([e for per_round in events for e in per_round], dtype=np.int64)
     applied = ev[((ev[:, 2] >> 8) == 0) & (ev[:, 0] != ev[:, 1])]  # apply_delta's records, as the device wrote them
     assert ((applied[:, 2] & 0xFF) >= 32).sum() > 100 and (applied[:, 2] & 0xFF).max() == 63
+
+
+def test_events_with_37_keys_canonical_prefix():
+    """37 keys in canonical prefix views (the KWB kernels with 10 of 16 key words in use): apply_cand's per-key path
+    reports keys up to index 36 and none past it."""
+    _, events = lockstep(warm_k37(), WARM_K37_KW, what="warm k37")
+    ev = np.asarray([e for per_round in events for e in per_round], dtype=np.int64)
+    applied = ev[((ev[:, 2] >> 8) == 0) & (ev[:, 0] != ev[:, 1])]
+    assert ((applied[:, 2] & 0xFF) >= 32).any() and (applied[:, 2] & 0xFF).max() == 36
 
 
 def test_events_with_16_keys_hb8mv8_escape_slots():

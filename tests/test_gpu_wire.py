@@ -21,7 +21,8 @@ pytestmark = pytest.mark.gpu
 
 CASES = [("trunc8", True), ("sched16", True), ("fdgc12", True), ("simple3", True), ("cold64", True),
          ("sched16", False), ("fdgc12", False),
-         ("bigval6", True), ("bigsleep12", True), ("bigsleep12", False)]  # 3-byte length prefixes, 64 KiB NodeDeltas
+         ("bigval6", True), ("bigsleep12", True), ("bigsleep12", False),  # 3-byte length prefixes, 64 KiB NodeDeltas
+         ("keys5", True), ("keys37", True), ("keys21w", True), ("keys21w", False)]  # K = 5, 37, 21 (gs_emit_delta<KWB>)
 
 
 @pytest.mark.parametrize("name,tomb", CASES)

@@ -2,8 +2,8 @@
 
 The golden fixtures pin the emitted bytes to the reference at up to 64 nodes
 (``test_gpu_wire.py``).  Here seeded 1,024-node (warm, canonical layout) and 256-node (cold,
-general layout) clusters run with a small MTU, so deltas are truncated; after several rounds
-the device's DigestPb and DeltaPb bytes are parsed and compared with the oracle's state and
+general layout) clusters, and smaller ones with 5, 37 and 64 keys, run with a small MTU, so
+deltas are truncated; after several rounds the device's DigestPb and DeltaPb bytes are parsed and compared with the oracle's state and
 with the oracle's ``compute_partial_delta_respecting_mtu`` restatement (``orc_kat_compute_delta``,
 pinned to the reference by ``tests/test_oracle_golden.py``): same NodeDeltas in the same order,
 same from_version_excluded, same kv versions; and every DeltaPb fits the MTU.  No node goes
@@ -45,7 +45,11 @@ def parse_delta(b, nid_index):
     return out
 
 
-@pytest.mark.parametrize("n,k,init,mtu", [(1024, 16, "warm", 3000), (256, 8, "cold", 2000)])
+@pytest.mark.parametrize("n,k,init,mtu", [(1024, 16, "warm", 3000), (256, 8, "cold", 2000),
+                                          # K = 5 (KP = 8), 37 (10 of the 16 key words) and 64 in the general layout;
+                                          # without churn a warm NodeDelta rarely has two kvs: at 37 keys the oracle
+                                          # cuts none at mtu 900 or 800, 134 at 300
+                                          (128, 5, "warm", 700), (128, 37, "warm", 300), (96, 64, "cold", 2600)])
 def test_emitter_matches_oracle_delta_at_size(n, k, init, mtu):
     spec = WorkloadSpec(n=n, k=k, fanout=3, seed=11, init=init, write_frac=0.3, down_frac=0.0)
     scen = make_scenario(f"wire{n}", spec, 8, {"mtu": mtu})

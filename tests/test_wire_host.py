@@ -18,7 +18,8 @@ from aiocluster_amd.pbsize import nodeid_size
 from aiocluster_amd.scenario import scenario_node_ids
 from aiocluster_amd.wire import frame, node_id_pb, packet, varint
 
-NAMES = ["trunc8", "sched16", "fdgc12", "simple3", "cold64", "bigval6", "bigsleep12"]
+NAMES = ["trunc8", "sched16", "fdgc12", "simple3", "cold64", "bigval6", "bigsleep12",
+         "keys5", "keys37", "keys21w"]
 
 
 def load_wire(name):
