@@ -78,6 +78,11 @@ COUNTER_FIELDS = [
     "pack_groups_max", "pack_steps_max",  # maxima (gs_read_counters takes the largest; sum_counters too)
     "heavy_slots",
 ]
+# Counters added after the ones above.  COUNTER_FIELDS is also the order of the counter vector that bench.py
+# --dump-outputs writes (counters.npy), which is compared across commits: it keeps its length, and later fields
+# are listed here (GossipSim.counters() returns both).
+COUNTER_FIELDS_MORE = ["cut_exchanges"]
+ALL_COUNTER_FIELDS = COUNTER_FIELDS + COUNTER_FIELDS_MORE
 
 # Every symbol include/gossip_sim.h declares (checked by tests/test_abi.py).
 EXPORTS = [
@@ -87,10 +92,10 @@ EXPORTS = [
     "gs_select_peers", "gs_schedule_phases", "gs_set_events", "gs_emit_scratch_bytes", "gs_emit_digest", "gs_emit_delta",
     "gs_check_heartbeat_lag", "gs_stream_copy", "gs_stream_read", "gs_stream_write", "gs_set_timing", "gs_kernel_times",
     "gs_phase_overflow", "gs_phase_chain", "gs_phase_pending", "gs_comm_id", "gs_comm_init", "gs_run_phase_group", "gs_read_rows",
-    "gs_latest_tick", "gs_flush_reports", "gs_set_ring_rows", "gs_mark", "gs_view_census",
+    "gs_latest_tick", "gs_flush_reports", "gs_set_ring_rows", "gs_mark", "gs_view_census", "gs_run_phase_cut", "gs_draw_cuts",
 ]
 
-API_VERSION = 22
+API_VERSION = 23
 MAX_PHASES = 64  # GS_MAX_PHASES
 MAX_SCHED_PHASES = 65536  # GS_MAX_SCHED_PHASES
 
@@ -122,7 +127,8 @@ class GsConfig(C.Structure):
 
 
 class GsCounters(C.Structure):
-    _fields_ = [(n, C.c_uint64) for n in COUNTER_FIELDS] + [("reserved", C.c_uint64 * (40 - len(COUNTER_FIELDS)))]
+    _fields_ = ([(n, C.c_uint64) for n in ALL_COUNTER_FIELDS]
+                + [("reserved", C.c_uint64 * (40 - len(ALL_COUNTER_FIELDS)))])
 
 
 CENSUS_FIELDS = ["up_pairs", "up_dead", "up_live", "down_pairs", "down_live"]
@@ -223,6 +229,8 @@ def load():
         "gs_owner_writes": (C.c_int, [P, P, u32, u32]),
         "gs_begin_round": (C.c_int, [P, P, u32]),
         "gs_run_phase": (C.c_int, [P, P, P, u32, u32]),
+        "gs_run_phase_cut": (C.c_int, [P, P, P, P, u32, u32]),
+        "gs_draw_cuts": (C.c_int, [P, P, P, u32, u64, u32, u32, u32, P]),
         "gs_liveness": (C.c_int, [P, P, u32]),
         "gs_phi_row": (C.c_int, [P, u32, u32, P]),
         "gs_read_counters": (C.c_int, [P, C.POINTER(GsCounters)]),

@@ -76,13 +76,13 @@ enum Ctr {
     C_EXCH = 0, C_REPORTS, C_ND, C_KVS, C_TRUNC, C_DBYTES, C_ALG, C_HBW, C_CAND, C_LIVE, C_TOMBGC,
     C_E_FDOVF, C_E_HIST, C_E_IDX, C_E_CONFLICT, C_E_FDGC, C_E_INSERT, C_FDGC, C_Q9, C_PACKB, C_E_HOLES,
     C_E_HBLAG, C_FLUSH /* host-side: plane_flushes */, C_FDSAT, C_LITE, C_SWEEPS /* host-side: lag_sweeps */,
-    C_LITEB, C_LIVEB, C_ESC, C_ESCREL, C_PGMAX, C_PSMAX, C_HEAVY,
+    C_LITEB, C_LIVEB, C_ESC, C_ESCREL, C_PGMAX, C_PSMAX, C_HEAVY, C_CUT,
     C_CEN0 = 40, C_NUM = C_CEN0 + 6  // gs_fd_census scratch slots (not part of gs_counters)
 };
 constexpr int CFIELDS = 40;  // gs_counters fields (the last ones reserved)
 constexpr int CROW = 48;     // u64 slots per counter shard row (the gs_counters fields, then the census scratch)
 static_assert(C_NUM <= CROW, "counter region");
-static_assert(C_HEAVY < CFIELDS, "gs_counters fields");
+static_assert(C_CUT < CFIELDS, "gs_counters fields");
 static_assert(sizeof(gs_counters) == CFIELDS * 8, "gs_counters layout");
 
 struct Dev {
@@ -191,6 +191,9 @@ struct Dev {
     // later slices hold the other columns)
     uint16_t *sm;
     uint32_t ev_wseq;  // owner-write ops issued since gs_set_events (the seq of the next call's op 0)
+    // cut exchanges (gs_run_phase_cut): legs[e] = messages delivered of exchange e; read by the CUT instantiations
+    // of the phase kernels only, which the host launches when it is set (set per phase; nullptr otherwise)
+    const uint8_t *legs;
 };
 
 // ------------------------------------------------------------------ protobuf sizes
@@ -1555,11 +1558,16 @@ __device__ __forceinline__ bool line_any8(bool w) {
 // (same appends, same order).
 // SCH = false: neither row can have a target scheduled for deletion at t (schA = schB = false; the
 // per-column predicates drop out).  SELF = false: the caller stores the responder's own new heartbeat.
-template <bool GENM, bool SCH = true, bool SELF = true, bool HB8 = false, bool MV8 = false>
+// CUT (gs_run_phase_cut): legs = messages delivered (wave-uniform).  b merges a's Syn digest only if the Syn
+// arrived (legs >= 1), a merges b's SynAck digest only if the SynAck did (legs >= 2), and a direction whose
+// delta is not delivered (b -> a: legs < 2, a -> b: legs < 3) has no stale owners, so the packers find nothing
+// to do for it.  A row that merges nothing still gets its plane words, all zero (the planes are never cleared).
+template <bool GENM, bool SCH = true, bool SELF = true, bool HB8 = false, bool MV8 = false, bool CUT = false>
 __device__ __forceinline__ void pass1_grp(const Dev &d, size_t ra, size_t rb, uint32_t c0, uint32_t a, uint32_t b,
                                           uint32_t t, bool schA, bool schB, Grp &g, uint32_t &nBA, uint32_t &nAB,
                                           uint32_t &nNB, uint32_t &nNA, uint32_t &alg, uint32_t &reports,
-                                          uint32_t &hbw, uint32_t &rmA, uint32_t &rmB) {
+                                          uint32_t &hbw, uint32_t &rmA, uint32_t &rmB, uint32_t legs = 3u) {
+    const bool syn = !CUT || legs >= 1u, synack = !CUT || legs >= 2u, ack = !CUT || legs >= 3u;
     bool dA = false, dB = false;
     rmA = rmB = 0u;
     nBA = nAB = nNB = nNA = 0u;
@@ -1584,7 +1592,7 @@ __device__ __forceinline__ void pass1_grp(const Dev &d, size_t ra, size_t rb, ui
         hB += isb ? 1u : 0u;
         if (SELF && isb) d.self_hb[j] = hB;
         // b: _report_heartbeat over a's digest (server.py:336-337, 599-604)
-        const bool mrgB = valid && inA && jg != b;
+        const bool mrgB = valid && inA && jg != b && syn;
         const bool newB = mrgB && !pb;
         const bool upB = mrgB && (newB || hA > hB);
         const bool repB = upB && pb && hB != 0u;
@@ -1592,7 +1600,7 @@ __device__ __forceinline__ void pass1_grp(const Dev &d, size_t ra, size_t rb, ui
         // a: _report_heartbeat over b's digest, computed after b's merge (server.py:340, 356-357)
         const bool pb2 = pb || newB;
         const bool inB = pb2 && !sb;  // j is in b's digest
-        const bool mrgA = valid && inB && jg != a;
+        const bool mrgA = valid && inB && jg != a && synack;
         const bool newA = mrgA && !pa;
         const bool upA = mrgA && (newA || hB > hA);
         const bool repA = upA && pa && hA != 0u;
@@ -1609,8 +1617,8 @@ __device__ __forceinline__ void pass1_grp(const Dev &d, size_t ra, size_t rb, ui
         const uint32_t mA = g.mA[i] & MV_MASK, mB = g.mB[i] & MV_MASK;
         const uint32_t dmA = inA ? mA : 0u;
         const uint32_t dmB = inB ? mB : 0u;
-        nBA |= (uint32_t)(valid && pb2 && !sb && mB > dmA) << i;
-        nAB |= (uint32_t)(valid && pa && !sa && mA > dmB) << i;
+        nBA |= (uint32_t)(valid && pb2 && !sb && mB > dmA && synack) << i;
+        nAB |= (uint32_t)(valid && pa && !sa && mA > dmB && ack) << i;
         nNB |= (uint32_t)newB << i;
         nNA |= (uint32_t)newA << i;
     }
@@ -1802,20 +1810,28 @@ __device__ __forceinline__ void group_pick(Dev &d, const GroupArgs *ga, const De
 // SPEC (not with FUSE): the speculative max-version merge of the recorded prefix candidates (spec_merge,
 // Dev::spec); k_settle then only settles the deltas that do not fit and the candidates with holes.
 // HB8 (not with FUSE): GS_HB8's 8-bit heartbeat views.
-template <int KW, bool FUSE, bool SPEC = false, bool HB8 = false, bool MV8 = false>
+// CUT (not with FUSE or SPEC): gs_run_phase_cut's instantiations (Dev::legs, pass1_grp<CUT>): a cut direction gets
+// no records, so k_lite and the packers find nothing to do for it.
+template <int KW, bool FUSE, bool SPEC = false, bool HB8 = false, bool MV8 = false, bool CUT = false>
 __global__ __launch_bounds__(XB, (KW == 4 ? (FUSE ? P1_WAVES : MV8 ? P1N_WAVES : P1S_WAVES) : 1)) void k_pass1(Dev d, const int32_t *ini, const int32_t *res,
                                                                        uint32_t n, uint32_t t, uint32_t seq,
                                                                        uint32_t e0) {
     static_assert(!(FUSE && SPEC), "the fused packer applies every NodeDelta itself");
     static_assert(!(FUSE && HB8), "8-bit heartbeats: record phases only");
+    static_assert(!(CUT && (FUSE || SPEC)), "cut exchanges: the plain record pass only");
     const uint32_t e = e0 + blockIdx.x;  // exchanges [e0, e0 + grid) of the phase (one chunk)
     if (e >= n) return;
     const int tid = threadIdx.x, lane = tid & (WAVE - 1), wid = tid >> 6;
     const int32_t ai = ini[e], bi = res[e];
-    if (ai < 0 || bi < 0 || (uint32_t)ai >= d.N || (uint32_t)bi >= d.N || ai == bi) {
+    // messages delivered (workgroup-uniform, kept scalar); above 3: a bad index, the exchange does nothing (its
+    // records count as none: the counts of an earlier phase may still stand in this exchange's slots)
+    const uint32_t legs = CUT ? (uint32_t)__builtin_amdgcn_readfirstlane((int)d.legs[e]) : 3u;
+    if (ai < 0 || bi < 0 || (uint32_t)ai >= d.N || (uint32_t)bi >= d.N || ai == bi || (CUT && legs > 3u)) {
         if (tid == 0) shard_add(d, C_E_IDX, 1);
+        if (CUT && lane == 0) d.cand_n[(size_t)e * 4 + 0 * 2 + wid] = d.cand_n[(size_t)e * 4 + 1 * 2 + wid] = 0u;
         return;
     }
+    if (CUT && tid == 0 && legs < 3u) shard_add(d, C_CUT, 1);
     const uint32_t a = (uint32_t)ai, b = (uint32_t)bi;
     if (tid == 0) {
         const uint32_t oa = atomicMax(&d.stamp[a], seq), ob = atomicMax(&d.stamp[b], seq);
@@ -1876,8 +1892,8 @@ __global__ __launch_bounds__(XB, (KW == 4 ? (FUSE ? P1_WAVES : MV8 ? P1N_WAVES :
             uint32_t rmA, rmB, nBA, nAB, nNB, nNA;
             const uint32_t mA[4] = {g0.mA[0], g0.mA[1], g0.mA[2], g0.mA[3]};
             const uint32_t mB[4] = {g0.mB[0], g0.mB[1], g0.mB[2], g0.mB[3]};
-            pass1_grp<false, SCH, false, HB8, MV8>(d, ra, rb, c0, a, b, t, schA, schB, g0, nBA, nAB, nNB, nNA, alg, reports, hbw,
-                                         rmA, rmB);
+            pass1_grp<false, SCH, false, HB8, MV8, CUT>(d, ra, rb, c0, a, b, t, schA, schB, g0, nBA, nAB, nNB, nNA, alg, reports, hbw,
+                                         rmA, rmB, legs);
             anynew = anynew || (nNB | nNA) != 0u;
             store_plane(planeA, c0, rmA, alg);
             store_plane(planeB, c0, rmB, alg);
@@ -2114,12 +2130,15 @@ struct P1vSlow {
     uint32_t gba[4], gab[4];  // bit 7 of byte i: the sender's max_version is the larger (b -> a: mB > mA; a -> b)
     uint32_t pA, pB, upA, upB, hbw, reports;
 };
+// CUT: a cut exchange runs here whole (k_pass1v's rslow), with pass1_grp<CUT>'s rules for `legs`.
+template <bool CUT = false>
 __device__ __noinline__ P1vSlow pass1v_slow(const uint32_t *self_pk, const uint8_t *fd_state, const uint32_t *tod,
                                             uint32_t delay, uint32_t col_lo, uint32_t ncol, size_t ra, size_t rb,
                                             uint32_t c, uint32_t a, uint32_t b, uint32_t t, bool schA, bool schB,
                                             uint4 hA4, uint4 hB4, uint4 mA4, uint4 mB4, const uint32_t *esc_slot,
-                                            uint16_t *esc16, uint32_t EC, const uint32_t *self_hb) {
+                                            uint16_t *esc16, uint32_t EC, const uint32_t *self_hb, uint32_t legs = 3u) {
     P1vSlow o{};
+    const bool syn = !CUT || legs >= 1u, synack = !CUT || legs >= 2u, ack = !CUT || legs >= 3u;
     const uint32_t x4[4] = {hA4.x, hA4.y, hA4.z, hA4.w}, y4[4] = {hB4.x, hB4.y, hB4.z, hB4.w};
     const uint32_t ma4[4] = {mA4.x, mA4.y, mA4.z, mA4.w}, mb4[4] = {mB4.x, mB4.y, mB4.z, mB4.w};
 #pragma unroll
@@ -2156,10 +2175,10 @@ __device__ __noinline__ P1vSlow pass1v_slow(const uint32_t *self_pk, const uint8
             const uint32_t mB = mv_dec8((mb4[q] >> (8 * i)) & 0xFFu, M) & MV_MASK;
             const bool isb = valid && jg == b;
             hB += isb ? 1u : 0u;  // responder inc_heartbeat (server.py:524)
-            const bool upB = valid && !sa && jg != b && hA > hB;  // b merges a's digest (server.py:336-337)
+            const bool upB = valid && !sa && jg != b && hA > hB && syn;  // b merges a's digest (server.py:336-337)
             const bool repB = upB && hB != 0u;                   // state.py:280-287
             hB = upB ? hA : hB;
-            const bool upA = valid && !sb && jg != a && hB > hA;  // then a merges b's (server.py:340, 356-357)
+            const bool upA = valid && !sb && jg != a && hB > hA && synack;  // then a merges b's (server.py:340, 356-357)
             const bool repA = upA && hA != 0u;
             hA = upA ? hB : hA;
             if (es != NONE) {
@@ -2175,8 +2194,8 @@ __device__ __noinline__ P1vSlow pass1v_slow(const uint32_t *self_pk, const uint8
             rB |= (uint32_t)repB << i;
             o.reports += (uint32_t)repA + (uint32_t)repB;
             // stale owners (state.py:347-357) against each side's digest
-            bA |= (uint32_t)(valid && !sb && mB > (sa ? 0u : mA)) << (8 * i + 7);  // b -> a
-            bB |= (uint32_t)(valid && !sa && mA > (sb ? 0u : mB)) << (8 * i + 7);  // a -> b
+            bA |= (uint32_t)(valid && !sb && mB > (sa ? 0u : mA) && synack) << (8 * i + 7);  // b -> a
+            bB |= (uint32_t)(valid && !sa && mA > (sb ? 0u : mB) && ack) << (8 * i + 7);  // a -> b
             gA |= (uint32_t)(mB > mA) << (8 * i + 7);
             gB |= (uint32_t)(mA > mB) << (8 * i + 7);
         }
@@ -2295,7 +2314,9 @@ __device__ __forceinline__ uint32_t lite_slot(const Dev &d, int32_t ai, int32_t 
 
 // LM >= 0: k_lite's slot work (lite_slot<LM>: 0 = one slice, 1 = a sliced count pass) runs in the same workgroup
 // after the stream, wave w taking direction w -- no k_lite launch (round 5; env GS_P1LITE=0: the launch of its own)
-template <int AHEAD, int LM, bool GRP = false>
+// CUT: gs_run_phase_cut's instantiations (Dev::legs).  An exchange with legs < 3 takes the per-column path whole
+// (rslow, pass1v_slow<CUT>); the intact exchanges of the same launch keep the byte-parallel loop.
+template <int AHEAD, int LM, bool GRP = false, bool CUT = false>
 __global__ __launch_bounds__(XB, P1V_WAVES) void k_pass1v(Dev d, const int32_t *ini, const int32_t *res, uint32_t n,
                                                           uint32_t t, uint32_t seq, SliceIO io, const GroupArgs *ga,
                                                           DevDyn dyn) {
@@ -2309,13 +2330,19 @@ __global__ __launch_bounds__(XB, P1V_WAVES) void k_pass1v(Dev d, const int32_t *
         io = ga->io[blockIdx.y];
     }
     // wid through readfirstlane: the half bounds, list and plane pointers derived from it stay scalar
+    static_assert(!(CUT && GRP), "cut exchanges: one-slice handles only");
     const int tid = threadIdx.x, lane = tid & (WAVE - 1), wid = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int32_t ai = ini[e], bi = res[e];
-    if (ai < 0 || bi < 0 || (uint32_t)ai >= d.N || (uint32_t)bi >= d.N || ai == bi) {
+    // messages delivered (workgroup-uniform, kept scalar); above 3: a bad index, the exchange does nothing (its
+    // records count as none: the counts of an earlier phase may still stand in this exchange's slots)
+    const uint32_t legs = CUT ? (uint32_t)__builtin_amdgcn_readfirstlane((int)d.legs[e]) : 3u;
+    if (ai < 0 || bi < 0 || (uint32_t)ai >= d.N || (uint32_t)bi >= d.N || ai == bi || (CUT && legs > 3u)) {
         if (tid == 0) shard_add(d, C_E_IDX, 1);
         if (LM >= 0 && lane == 0) d.slot_stat[(size_t)e * 2 + wid].w = LITE_DONE;  // (as k_lite: counted already)
+        if (CUT && lane == 0) d.cand_n[(size_t)e * 4 + 0 * 2 + wid] = d.cand_n[(size_t)e * 4 + 1 * 2 + wid] = 0u;
         return;
     }
+    if (CUT && tid == 0 && legs < 3u) shard_add(d, C_CUT, 1);
     const uint32_t a = (uint32_t)ai, b = (uint32_t)bi;
     if (tid == 0) {
         const uint32_t oa = atomicMax(&d.stamp[a], seq), ob = atomicMax(&d.stamp[b], seq);
@@ -2325,7 +2352,7 @@ __global__ __launch_bounds__(XB, P1V_WAVES) void k_pass1v(Dev d, const int32_t *
     const uint4 rowB = *reinterpret_cast<const uint4 *>(d.row + (size_t)b * 4);
     const bool schA = t >= rowA.z, schB = t >= rowB.z;
     // the whole exchange on the per-column path: a row that may hold a target scheduled for deletion, or a hot row
-    const bool rslow = schA || schB || ((rowA.w | rowB.w) & 4u);
+    const bool rslow = schA || schB || ((rowA.w | rowB.w) & 4u) || (CUT && legs < 3u);
     const size_t ra = (size_t)a * d.NP, rb = (size_t)b * d.NP;
     const uint32_t words = d.NP / 32;
     uint16_t *gBA = reinterpret_cast<uint16_t *>(d.sbits + (size_t)e * 2 * words), *gAB = gBA + 2 * words;
@@ -2381,8 +2408,8 @@ __global__ __launch_bounds__(XB, P1V_WAVES) void k_pass1v(Dev d, const int32_t *
         return rslow || (fl >> 16) || c + 16u > d.ncol || ja - c < 16u || jb - c < 16u;
     };
     auto slow_group = [&](uint32_t c, const V16 &v) {
-        const P1vSlow o = pass1v_slow(d.self_pk, d.fd_state, d.tod, d.sched_delay, d.col_lo, d.ncol, ra, rb, c, a, b,
-                                      t, schA, schB, v.hA, v.hB, v.mA, v.mB, d.esc_slot, d.esc16, d.EC, d.self_hb);
+        const P1vSlow o = pass1v_slow<CUT>(d.self_pk, d.fd_state, d.tod, d.sched_delay, d.col_lo, d.ncol, ra, rb, c, a, b,
+                                           t, schA, schB, v.hA, v.hB, v.mA, v.mB, d.esc_slot, d.esc16, d.EC, d.self_hb, legs);
         if (hbst) {
             if (o.upA) *reinterpret_cast<uint4 *>(hw8 + ra + c) = make_uint4(o.nwA[0], o.nwA[1], o.nwA[2], o.nwA[3]);
             if (o.upB) *reinterpret_cast<uint4 *>(hw8 + rb + c) = make_uint4(o.nwB[0], o.nwB[1], o.nwB[2], o.nwB[3]);
@@ -2637,7 +2664,11 @@ __global__ __launch_bounds__(XB, P1V_WAVES) void k_pass1v(Dev d, const int32_t *
         // wave w sizes / completes direction w (0: the SynAck delta b -> a, 1: the Ack delta a -> b) as k_lite
         // would, while the other workgroups on the CU stream their rows
         __syncthreads();
-        lite_slot<LM>(d, ai, bi, n, t, io, (size_t)e * 2 + wid, wid, lane);
+        if (CUT && legs < (wid == 0 ? 2u : 3u)) {  // a cut direction: nothing to size or pack (wave-uniform)
+            if (lane == 0) d.slot_stat[(size_t)e * 2 + wid].w = LITE_DONE;
+        } else {
+            lite_slot<LM>(d, ai, bi, n, t, io, (size_t)e * 2 + wid, wid, lane);
+        }
     }
 }
 // After a k_pass1v phase: the responders' small bits (their own heartbeat rose by one in the phase; pass 1
@@ -2653,18 +2684,23 @@ __global__ __launch_bounds__(LB) void k_p1v_fix(Dev d, const int32_t *res, uint3
 }
 
 // MODE 0: the whole exchange (one slice).  MODE 1: sharded count pass (pass 1, then the slice totals).
-template <int KW, bool GENM, int MODE>
+// CUT (MODE 0): gs_run_phase_cut's instantiations (Dev::legs, pass1_grp<CUT>); a cut direction's wave skips pass 3.
+template <int KW, bool GENM, int MODE, bool CUT = false>
 __global__ __launch_bounds__(XB, (KW == 4 ? XB_WAVES : 1)) void k_exchange(Dev d, const int32_t *ini, const int32_t *res, uint32_t n,
                                                  uint32_t t, uint32_t seq, SliceIO io) {
+    static_assert(!(CUT && MODE != 0), "cut exchanges: one-slice handles only");
     extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
     const uint32_t e = blockIdx.x;
     if (e >= n) return;
     const int tid = threadIdx.x, lane = tid & (WAVE - 1), wid = tid >> 6;
     const int32_t ai = ini[e], bi = res[e];
-    if (ai < 0 || bi < 0 || (uint32_t)ai >= d.N || (uint32_t)bi >= d.N || ai == bi) {
+    // messages delivered (workgroup-uniform, kept scalar); above 3: a bad index, the exchange does nothing
+    const uint32_t legs = CUT ? (uint32_t)__builtin_amdgcn_readfirstlane((int)d.legs[e]) : 3u;
+    if (ai < 0 || bi < 0 || (uint32_t)ai >= d.N || (uint32_t)bi >= d.N || ai == bi || (CUT && legs > 3u)) {
         if (tid == 0) shard_add(d, C_E_IDX, 1);
         return;
     }
+    if (CUT && tid == 0 && legs < 3u) shard_add(d, C_CUT, 1);
     const uint32_t a = (uint32_t)ai, b = (uint32_t)bi;
     constexpr bool genm = GENM;
     const uint32_t words = d.NP / 32;
@@ -2713,7 +2749,8 @@ __global__ __launch_bounds__(XB, (KW == 4 ? XB_WAVES : 1)) void k_exchange(Dev d
         Grp g0;
         dec_grp(r0, g0);
         uint32_t rmA, rmB, nBA, nAB, nNB, nNA;
-        pass1_grp<GENM>(d, ra, rb, c0, a, b, t, schA, schB, g0, nBA, nAB, nNB, nNA, alg, reports, hbw, rmA, rmB);
+        pass1_grp<GENM, true, true, false, false, CUT>(d, ra, rb, c0, a, b, t, schA, schB, g0, nBA, nAB, nNB, nNA, alg,
+                                                       reports, hbw, rmA, rmB, legs);
         // one LDS atomic per lane and bitmap (4 consecutive columns sit in one word); stale owners are sparse
         const uint32_t sh = c0 & 31u;
         if (nBA) atomicOr(&bBA[c0 >> 5], nBA << sh);
@@ -2796,7 +2833,7 @@ __global__ __launch_bounds__(XB, (KW == 4 ? XB_WAVES : 1)) void k_exchange(Dev d
     // ---- pass 3: SynAck delta b -> a (wave 0) and Ack delta a -> b (wave 1), each applied
     WStats st{0, 0, 0, 0, 0};
     bool tomb = false;
-    if (!(d.ablate & 1u)) {
+    if (!(d.ablate & 1u) && !(CUT && legs < (wid == 0 ? 2u : 3u))) {  // (a cut direction packs nothing)
         const bool w0 = wid == 0;  // wave-uniform: one call site, so pack_dir inlines
         const uint32_t snd = w0 ? b : a, rcv = w0 ? a : b;
         const DigestSide ds{rcv, w0 ? cntA0 : cntB, w0 ? schA : schB};
@@ -5226,6 +5263,18 @@ __host__ __device__ inline double unit53(uint32_t a, uint32_t b) {
     return (double)(((uint64_t)a << 21) ^ (uint64_t)(b >> 11)) * (1.0 / 9007199254740992.0);
 }
 
+// gs_draw_cuts: independent message loss, one thread per exchange.  Message m of the exchange is lost iff word m
+// of Philox(key = seed, counter = (round, initiator, responder, phase)) is below loss_q32; legs = the messages
+// delivered before the first lost one.  Restated on the CPU by aiocluster_amd/cuts.py.
+__global__ __launch_bounds__(LB) void k_draw_cuts(const int32_t *ini, const int32_t *res, uint32_t n, uint64_t seed,
+                                                  uint32_t round, uint32_t phase, uint32_t loss_q32, uint8_t *legs) {
+    const uint32_t e = blockIdx.x * LB + threadIdx.x;
+    if (e >= n) return;
+    uint32_t c[4] = {round, (uint32_t)ini[e], (uint32_t)res[e], phase};
+    philox4x32(c, (uint32_t)seed, (uint32_t)(seed >> 32));
+    legs[e] = c[0] < loss_q32 ? 0u : c[1] < loss_q32 ? 1u : c[2] < loss_q32 ? 2u : 3u;
+}
+
 // per row: live / dead / known-peer counts (observer up); SCNT[o] = {live, dead, peers, 0}
 __global__ __launch_bounds__(LB) void k_sel_count(Dev d, const uint8_t *up, uint32_t *scnt) {
     const uint32_t o = blockIdx.x;
@@ -5962,10 +6011,10 @@ int launch_lite(gs_handle *h, const int32_t *ini, const int32_t *res, uint32_t n
     return time_end(h, GS_KT_LITE, e0);
 }
 
-template <int KW, bool GENM, int MODE>
+template <int KW, bool GENM, int MODE, bool CUT = false>
 int launch_exchange(gs_handle *h, const int32_t *ini, const int32_t *res, uint32_t n, uint32_t tick, size_t lds,
                     const SliceIO &io) {
-    auto *k = k_exchange<KW, GENM, MODE>;
+    auto *k = k_exchange<KW, GENM, MODE, CUT>;
     if (lds > 64 * 1024)
         HIPCHK(h, hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     k<<<n, XB, lds, h->stream>>>(h->d, ini, res, n, tick, h->seq, io);
@@ -6084,6 +6133,23 @@ int launch_pass1(gs_handle *h, const int32_t *ini, const int32_t *res, uint32_t 
     hipEvent_t e0 = nullptr;
     int rc = time_begin(h, e0);
     if (rc) return rc;
+    if (h->d.legs) {  // gs_run_phase_cut (one slice, GS_PACK's default mode: checked there): the CUT instantiations
+        if (h->d.pl16) {
+            if (lm == 0) k_pass1v<P1V_AHEAD, 0, false, true><<<n, XB, 0, h->stream>>>(h->d, ini, res, n, tick, h->seq, io, nullptr, DevDyn{});
+            else k_pass1v<P1V_AHEAD, -1, false, true><<<n, XB, 0, h->stream>>>(h->d, ini, res, n, tick, h->seq, io, nullptr, DevDyn{});
+            HIPCHK(h, hipGetLastError());
+            rc = time_end(h, GS_KT_PASS1, e0);
+            if (rc) return rc;
+            if (defer_fix) return GS_OK;
+            k_p1v_fix<<<(n + LB - 1) / LB, LB, 0, h->stream>>>(h->d, res, n);
+            HIPCHK(h, hipGetLastError());
+            return GS_OK;
+        }
+        if (h->d.hb8) k_pass1<4, false, false, true, false, true><<<n, XB, 0, h->stream>>>(h->d, ini, res, n, tick, h->seq, 0u);
+        else k_pass1<4, false, false, false, false, true><<<n, XB, 0, h->stream>>>(h->d, ini, res, n, tick, h->seq, 0u);
+        HIPCHK(h, hipGetLastError());
+        return time_end(h, GS_KT_PASS1, e0);
+    }
     if (h->d.pl16) {  // GS_MV8 record phases: the byte-parallel pass 1
         const dim3 grid(n, gx.nh);
         if (gx.ga && lm == 1) k_pass1v<P1V_AHEAD, 1, true><<<grid, XB, 0, h->stream>>>(h->d, ini, res, n, tick, h->seq, io, gx.ga, gx.dyn);
@@ -6169,6 +6235,7 @@ uint32_t heavy_t() {
 int run_split_phase(gs_handle *h, const int32_t *ini, const int32_t *res, uint32_t n, uint32_t tick) {
     hipEvent_t e0 = nullptr;
     int rc;
+    // (a cut phase keeps the speculative merge: a cut direction has no records, so nothing of it is merged)
     h->d.spec = spec_ok(h) || spec_v_ok(h) ? 1u : 0u;
     h->d.lite = lite_ok(h) ? 1u : 0u;
     if (h->pack_mode == 1) {
@@ -6593,7 +6660,37 @@ int sliced_phase(gs_handle *const *hs, uint32_t nh, const int32_t *ini, const in
 }
 }
 
+extern "C++" {
+namespace {
+// gs_run_phase (legs = nullptr) and gs_run_phase_cut: Dev::legs selects the CUT instantiations for this phase's launches
+int run_phase(gs_handle *h, const int32_t *ini, const int32_t *res, const uint8_t *legs, uint32_t n, uint32_t tick);
+}
+}
+
 int gs_run_phase(gs_handle *h, const int32_t *ini, const int32_t *res, uint32_t n, uint32_t tick) {
+    return run_phase(h, ini, res, nullptr, n, tick);
+}
+
+int gs_run_phase_cut(gs_handle *h, const int32_t *ini, const int32_t *res, const uint8_t *legs, uint32_t n,
+                     uint32_t tick) {
+    if (!legs) return run_phase(h, ini, res, nullptr, n, tick);
+    if (!h || !h->booted) return GS_E_INVALID;
+    if (h->sliced || h->G > 1 || h->comm)
+        return fail(h, GS_E_UNSUPPORTED, "gs_run_phase_cut: cut exchanges run on one-slice handles only");
+    // the phase variants that do not know cuts (A/B env settings): refused, never run with the cuts ignored
+    if (h->split && h->pack_mode != 2)
+        return fail(h, GS_E_UNSUPPORTED, "gs_run_phase_cut: GS_PACK=fused / spec phases do not know cut exchanges");
+    if (h->d.mv8 && !h->d.pl16)
+        return fail(h, GS_E_UNSUPPORTED, "gs_run_phase_cut: GS_P1=old phases do not know cut exchanges");
+    h->d.legs = legs;
+    const int rc = run_phase(h, ini, res, legs, n, tick);
+    h->d.legs = nullptr;
+    return rc;
+}
+
+extern "C++" {
+namespace {
+int run_phase(gs_handle *h, const int32_t *ini, const int32_t *res, const uint8_t *legs, uint32_t n, uint32_t tick) {
     int rc = check_phase(h, ini, res, n, tick);
     if (rc) return rc;
     if (h->sliced) {
@@ -6617,11 +6714,29 @@ int gs_run_phase(gs_handle *h, const int32_t *ini, const int32_t *res, uint32_t 
     h->d.lite = 0u;
     hipEvent_t e0 = nullptr;
     if ((rc = time_begin(h, e0))) return rc;
-    if (h->KP <= 16) rc = genm ? launch_exchange<4, true, 0>(h, ini, res, n, tick, lds, io)
-                               : launch_exchange<4, false, 0>(h, ini, res, n, tick, lds, io);
-    else rc = genm ? launch_exchange<KWB, true, 0>(h, ini, res, n, tick, lds, io)
-                   : launch_exchange<KWB, false, 0>(h, ini, res, n, tick, lds, io);
+    if (legs) {
+        if (h->KP <= 16) rc = genm ? launch_exchange<4, true, 0, true>(h, ini, res, n, tick, lds, io)
+                                   : launch_exchange<4, false, 0, true>(h, ini, res, n, tick, lds, io);
+        else rc = genm ? launch_exchange<KWB, true, 0, true>(h, ini, res, n, tick, lds, io)
+                       : launch_exchange<KWB, false, 0, true>(h, ini, res, n, tick, lds, io);
+    } else {
+        if (h->KP <= 16) rc = genm ? launch_exchange<4, true, 0>(h, ini, res, n, tick, lds, io)
+                                   : launch_exchange<4, false, 0>(h, ini, res, n, tick, lds, io);
+        else rc = genm ? launch_exchange<KWB, true, 0>(h, ini, res, n, tick, lds, io)
+                       : launch_exchange<KWB, false, 0>(h, ini, res, n, tick, lds, io);
+    }
     return rc ? rc : time_end(h, GS_KT_PASS1, e0);
+}
+}  // namespace
+}
+
+int gs_draw_cuts(gs_handle *h, const int32_t *ini, const int32_t *res, uint32_t n, uint64_t seed, uint32_t round,
+                 uint32_t phase, uint32_t loss_q32, uint8_t *legs) {
+    if (!h || (n && (!ini || !res || !legs))) return GS_E_INVALID;
+    if (!n) return GS_OK;
+    k_draw_cuts<<<(n + LB - 1) / LB, LB, 0, h->stream>>>(ini, res, n, seed, round, phase, loss_q32, legs);
+    HIPCHK(h, hipGetLastError());
+    return GS_OK;
 }
 
 int gs_shard_columns(const gs_handle *h, uint32_t *col_lo, uint32_t *n_cols) {

@@ -6,6 +6,11 @@ on the slices a process holds, in the order ``Cluster._gossip_multiple`` runs it
 (``aiocluster/server.py:441-495``): owner writes, ``inc_heartbeat`` + tombstone GC
 (``gs_begin_round``), the conflict-free phases (``gs_run_phase``, or the sliced
 count/gather/pack of ``shard.py``), then ``_update_node_liveness`` (``gs_liveness``).
+
+With ``WorkloadSpec.loss > 0`` every phase carries a device ``legs`` tensor (``rd["legs"]``, parallel to
+``rd["phases"]``: the messages delivered of each exchange, ``aiocluster_amd.cuts``) and runs through
+``gs_run_phase_cut``; with peer-selected rounds the legs are drawn on the device (``gs_draw_cuts``).  With
+``loss == 0`` nothing changes.
 """
 
 from __future__ import annotations
@@ -36,8 +41,10 @@ def boot_ops(n: int, k: int) -> list[np.ndarray]:
 def prepare(spec, rounds: int, torch, dev) -> list[dict]:
     """Every round's device inputs (host schedule generation is not timed).  Write values are
     interned as ids 2^24 + i with the byte length of ``workload.write_value``."""
+    from .cuts import draw_cuts_q32, loss_q32
     from .workload import OP_DELETE, OP_DELETE_AFTER_TTL, Workload, liveness_tick, phase_tick, round_tick
 
+    q32 = loss_q32(spec.loss)
     wl = Workload(spec)
     out = []
     vid = 1 << 24
@@ -67,6 +74,10 @@ def prepare(spec, rounds: int, torch, dev) -> list[dict]:
             "t_live": liveness_tick(r, len(p.phases)),
             "exchanges": p.n_exchanges,
         })
+        if q32:  # message loss: the legs of every phase, from the host mirror of gs_draw_cuts
+            out[-1]["legs"] = [torch.from_numpy(draw_cuts_q32(a, b, spec.cut_seed, r, i, q32)).to(dev)
+                               for i, (a, b) in enumerate(p.phases)]
+            out[-1]["loss_q32"], out[-1]["cut_seed"] = q32, spec.cut_seed
     return out
 
 
@@ -79,10 +90,15 @@ def begin(sims, rd):
         sim._chk(sim.L.gs_begin_round(sim.h, C.c_void_p(rd["up"].data_ptr()), rd["t"]), "gs_begin_round")
 
 
-def run_phases(sims, rd, events=None, group=None, phases=None):
-    """The round's phases (``phases`` overrides the plan's: (a, b, n, tick) tuples)."""
+def run_phases(sims, rd, events=None, group=None, phases=None, legs=None):
+    """The round's phases (``phases`` overrides the plan's: (a, b, n, tick) tuples; ``legs``: one device u8 tensor
+    per phase, default the plan's ``rd["legs"]`` for the plan's phases)."""
     s0 = sims[0]
-    for a, b, n, t in (rd["phases"] if phases is None else phases):
+    if phases is None and legs is None:
+        legs = rd.get("legs")
+    if legs is not None and group is not None:
+        raise ValueError("cut exchanges (loss > 0) run on one-slice handles only")
+    for i, (a, b, n, t) in enumerate(rd["phases"] if phases is None else phases):
         if not n:
             continue
         for s_ in sims:
@@ -94,7 +110,10 @@ def run_phases(sims, rd, events=None, group=None, phases=None):
             e0 = s0.torch.cuda.Event(enable_timing=True)
             e1 = s0.torch.cuda.Event(enable_timing=True)
             e0.record(s0.stream)
-        if group is None:
+        if legs is not None:
+            s0._chk(s0.L.gs_run_phase_cut(s0.h, C.c_void_p(a.data_ptr()), C.c_void_p(b.data_ptr()),
+                                          C.c_void_p(legs[i].data_ptr()), n, t), "gs_run_phase_cut")
+        elif group is None:
             s0._chk(s0.L.gs_run_phase(s0.h, C.c_void_p(a.data_ptr()), C.c_void_p(b.data_ptr()), n, t),
                     "gs_run_phase")
         else:  # the group's own driver: shard.py's (its scratch kept across phases), or the library's (native)
@@ -118,7 +137,7 @@ def run_round(sims, rd, events=None, group=None, sel=None):
     from .workload import TICKS_PER_ROUND, liveness_tick, phase_tick
 
     begin(sims, rd)
-    phases = None
+    phases = legs = None
     if sel is not None:
         sel.select(rd["up"], rd["r"])
         ph, offs, left = sel.schedule(rd["up"], rd["r"])
@@ -127,7 +146,10 @@ def run_round(sims, rd, events=None, group=None, sel=None):
         rd["unscheduled"] = left
         rd["t_live"] = liveness_tick(rd["r"], len(phases))  # sub-phases share the budget's last tick
         rd["phases_run"] = len(phases)
+        if rd.get("loss_q32"):  # message loss over the scheduled phases, drawn on the device
+            legs = [sims[0].draw_cuts(a, b, rd["cut_seed"], rd["r"], p, rd["loss_q32"])
+                    for p, (a, b, n) in enumerate(ph)]
     if rd["t_live"] >= rd["t"] + TICKS_PER_ROUND:
         raise ValueError(f"round {rd['r']}: liveness tick {rd['t_live']} reaches the next round's tick")
-    run_phases(sims, rd, events, group, phases)
+    run_phases(sims, rd, events, group, phases, legs)
     end(sims, rd)

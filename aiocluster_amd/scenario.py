@@ -135,7 +135,9 @@ def round_ticks(scen: dict, r: int) -> list[int]:
 
 
 def replay_round(backend, scen: dict, r: int):
-    """Round ``r`` of ``scen`` on ``backend`` (writes, round start, phases, liveness)."""
+    """Round ``r`` of ``scen`` on ``backend`` (writes, round start, phases, liveness).  A round may carry
+    ``"legs"``: one list per phase, parallel to ``"phases"`` -- the messages delivered of each exchange
+    (aiocluster_amd.cuts); such a round's phases run as ``backend.run_phase(t, pairs, legs)``."""
     rd = scen["rounds"][r]
     t = round_tick(r)
     up = rd["up"]
@@ -143,6 +145,12 @@ def replay_round(backend, scen: dict, r: int):
     for j, k, op, v in rd["writes"]:
         backend.write(t, j, k, op, v)
     backend.begin_round(t, up)
+    legs = rd.get("legs")
+    if legs is not None and len(legs) != len(rd["phases"]):
+        raise ValueError(f"round {r}: {len(legs)} legs lists for {len(rd['phases'])} phases")
     for p, ph in enumerate(rd["phases"]):
-        backend.run_phase(ticks[p], ph)
+        if legs is None:
+            backend.run_phase(ticks[p], ph)
+        else:
+            backend.run_phase(ticks[p], ph, legs[p])
     backend.liveness(ticks[-1], up, r)

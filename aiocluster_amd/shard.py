@@ -266,13 +266,19 @@ class ShardGroup:
         for s in self.slices:
             s.begin_round(t, up)
 
-    def run_phase(self, t: int, pairs):
+    def run_phase(self, t: int, pairs, legs=None):
+        if legs is not None:
+            raise GsError("cut exchanges (legs) run on one-slice handles only: a ShardGroup's sliced phases do not "
+                          "support them")
         if len(pairs) == 0:
             return
         arr = np.asarray(pairs, dtype=np.int32).reshape(-1, 2)
         self.run_phase_arrays(t, arr[:, 0], arr[:, 1])
 
-    def run_phase_arrays(self, t: int, initiators, responders):
+    def run_phase_arrays(self, t: int, initiators, responders, legs=None):
+        if legs is not None:
+            raise GsError("cut exchanges (legs) run on one-slice handles only: a ShardGroup's sliced phases do not "
+                          "support them")
         s0 = self.slices[0]
         for s in self.slices:
             s._flush()

@@ -369,12 +369,14 @@ class GossipSim:
         u = up if hasattr(up, "data_ptr") else self._dev(np.asarray(up, dtype=np.uint8), self.torch.uint8)
         self._chk(self.L.gs_begin_round(self.h, C.c_void_p(u.data_ptr()), t), "gs_begin_round")
 
-    def run_phase(self, t: int, pairs):
+    def run_phase(self, t: int, pairs, legs=None):
+        """One phase of exchanges; ``legs`` (one value 0-3 per pair: the messages delivered, aiocluster_amd.cuts)
+        runs it through gs_run_phase_cut."""
         self._flush()
         if len(pairs) == 0:
             return
         arr = np.asarray(pairs, dtype=np.int32).reshape(-1, 2)
-        self.run_phase_arrays(t, arr[:, 0], arr[:, 1])
+        self.run_phase_arrays(t, arr[:, 0], arr[:, 1], legs)
 
     def _pairs_dev(self, initiators, responders):
         ini = initiators if hasattr(initiators, "data_ptr") else self._dev(np.asarray(initiators, np.int32),
@@ -383,7 +385,7 @@ class GossipSim:
                                                                            self.torch.int32)
         return ini, res
 
-    def run_phase_arrays(self, t: int, initiators, responders):
+    def run_phase_arrays(self, t: int, initiators, responders, legs=None):
         if self.sliced:
             raise GsError("a column slice runs phases through ShardGroup (gs_phase_count / gs_phase_pack)")
         ini, res = self._pairs_dev(initiators, responders)
@@ -392,8 +394,25 @@ class GossipSim:
             return
         if self._ev is not None:
             self._ev_note_phase(ini, res)
-        self._chk(self.L.gs_run_phase(self.h, C.c_void_p(ini.data_ptr()), C.c_void_p(res.data_ptr()), n, t),
-                  "gs_run_phase")
+        if legs is None:
+            self._chk(self.L.gs_run_phase(self.h, C.c_void_p(ini.data_ptr()), C.c_void_p(res.data_ptr()), n, t),
+                      "gs_run_phase")
+            return
+        lg = legs if hasattr(legs, "data_ptr") else self._dev(np.asarray(legs, np.uint8), self.torch.uint8)
+        if lg.dtype != self.torch.uint8 or int(lg.numel()) != n:
+            raise GsError(f"legs: one uint8 per exchange (got {int(lg.numel())} {lg.dtype} for {n} exchanges)")
+        self._chk(self.L.gs_run_phase_cut(self.h, C.c_void_p(ini.data_ptr()), C.c_void_p(res.data_ptr()),
+                                          C.c_void_p(lg.data_ptr()), n, t), "gs_run_phase_cut")
+
+    def draw_cuts(self, initiators, responders, seed: int, rnd: int, phase: int, loss_q32: int, out=None):
+        """gs_draw_cuts: the device u8 legs of one phase under independent message loss (aiocluster_amd.cuts)."""
+        ini, res = self._pairs_dev(initiators, responders)
+        n = int(ini.numel())
+        if out is None:
+            out = self.torch.empty(n, dtype=self.torch.uint8, device=self.device)
+        self._chk(self.L.gs_draw_cuts(self.h, C.c_void_p(ini.data_ptr()), C.c_void_p(res.data_ptr()), n, seed, rnd,
+                                      phase, loss_q32, C.c_void_p(out.data_ptr())), "gs_draw_cuts")
+        return out
 
     # ------------------------------------------------------- sliced phases (shards > 1)
     def phase_count(self, t: int, ini, res, out=None):
@@ -467,7 +486,7 @@ class GossipSim:
     def counters(self) -> dict:
         c = _lib.GsCounters()
         self._chk(self.L.gs_read_counters(self.h, C.byref(c)), "gs_read_counters")
-        return {n: int(getattr(c, n)) for n in _lib.COUNTER_FIELDS}
+        return {n: int(getattr(c, n)) for n in _lib.ALL_COUNTER_FIELDS}
 
     def reset_counters(self):
         self._chk(self.L.gs_reset_counters(self.h), "gs_reset_counters")

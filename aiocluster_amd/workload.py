@@ -144,6 +144,10 @@ class WorkloadSpec:
     node_style: str = "synthetic"
     initial_keys: int | None = None  # keys written at boot (default: all k)
     quiet_from: int | None = None  # rounds >= this: no writes, every node up (convergence checks)
+    # independent message loss (aiocluster_amd.cuts): each Syn / SynAck / Ack of an exchange is lost with this
+    # probability, drawn from cut_seed; the schedule itself does not change (driver.prepare adds the legs)
+    loss: float = 0.0
+    cut_seed: int = 0
     extra: dict = field(default_factory=dict)
 
 

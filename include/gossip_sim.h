@@ -28,7 +28,7 @@
 extern "C" {
 #endif
 
-#define GS_API_VERSION 22
+#define GS_API_VERSION 23
 #define GS_MAX_PHASES 64  /* report bit planes' phases per plane base window of the scheduler (busy bits) */
 /* gs_schedule_phases: phases of one round's schedule.  Every selected exchange runs (server.py:476-493): phases
  * past the workload's tick budget are sub-phases, run at one tick (gs_run_phase at the previous phase's tick). */
@@ -251,7 +251,8 @@ typedef struct gs_counters {
                                   critical path */
     uint64_t heavy_slots;      /* (exchange, direction) slots the exact packer handed to its heavy-slot kernel
                                   (k_pack_heavy: more stale owners than the hand-off threshold) */
-    uint64_t reserved[7];
+    uint64_t cut_exchanges;    /* exchanges gs_run_phase_cut ran with fewer than 3 messages delivered (legs < 3) */
+    uint64_t reserved[6];
 } gs_counters;
 
 /* Failure-detector membership census (gs_fd_census): (observer, target) pairs with the observer up and
@@ -313,6 +314,22 @@ int gs_begin_round(gs_handle *h, const uint8_t *up, uint32_t tick);
  * window in between); a phase past the planes' base's GS_PLANES planes replays the pending planes into the
  * windows first (counted in plane_flushes). */
 int gs_run_phase(gs_handle *h, const int32_t *initiators, const int32_t *responders, uint32_t n, uint32_t tick);
+/* gs_run_phase with per-exchange cuts: DEVICE u8 legs[n] = messages delivered of exchange e (NULL = all 3 =
+ * gs_run_phase, bit for bit).  3: intact.  2: the Ack is lost -- b merges a's digest and a applies the SynAck
+ * delta, b applies nothing (server.py:372-376 does not run).  1: the SynAck is lost -- b's own heartbeat + 1 and
+ * b's _report_heartbeat over a's Syn digest (server.py:524, 334-348); a is untouched.  0: the Syn is never
+ * read -- b's own heartbeat + 1 only.  A value above 3 is counted in err_bad_index and that exchange does
+ * nothing.  Counters count what was delivered (a cut delta is neither packed nor counted); cut_exchanges
+ * counts the exchanges with legs < 3.  Every phase rule of gs_run_phase holds unchanged.  One-slice handles
+ * only: with legs != NULL a sliced handle, and the phase variants that do not know cuts (env GS_PACK=fused /
+ * spec), return GS_E_UNSUPPORTED. */
+int gs_run_phase_cut(gs_handle *h, const int32_t *initiators, const int32_t *responders, const uint8_t *legs,
+                     uint32_t n, uint32_t tick);
+/* Independent message loss, asynchronous on h's stream: message m (0 = Syn, 1 = SynAck, 2 = Ack) of exchange e
+ * is lost iff word m of Philox4x32-10(key = seed, counter = (round, initiator, responder, phase)) is
+ * < loss_q32; legs[e] (DEVICE u8[n]) = messages delivered before the first lost one.  loss_q32 = 0: all 3. */
+int gs_draw_cuts(gs_handle *h, const int32_t *initiators, const int32_t *responders, uint32_t n, uint64_t seed,
+                 uint32_t round, uint32_t phase, uint32_t loss_q32, uint8_t *legs);
 /* Owner-column sliced phase (n_shards > 1; gs_run_phase refuses sliced handles).  The slices of one
  * cluster run, per phase, on the same initiators/responders:
  *   1. gs_phase_count: pass 1 of every exchange on this slice's columns (heartbeats, failure-detector

@@ -39,6 +39,9 @@ def main():
     ap.add_argument("--partition", type=int, default=30)
     ap.add_argument("--heal", type=int, default=30)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--loss", type=float, default=0.0,
+                    help="probability that a Syn / SynAck / Ack is lost (gs_run_phase_cut): the false-positive rate "
+                         "under message loss")
     args = ap.parse_args()
 
     import torch
@@ -55,7 +58,8 @@ def main():
     cfg = dict(DEFAULT_CFG)
     cfg["tombstone_grace_s"] = 10
     spec = WorkloadSpec(n=n, k=K, fanout=args.fanout, seed=args.seed, init="warm", write_frac=0.05,
-                        delete_frac=0.01, partition=(args.warm, args.warm + args.partition))
+                        delete_frac=0.01, partition=(args.warm, args.warm + args.partition), loss=args.loss,
+                        cut_seed=args.seed)
     boot = boot_ops(n, K)
     t0 = time.perf_counter()
     sim = GossipSim(synthetic_node_ids(n), key_names(K), cfg, init="warm", device=str(dev), tombstones=True,
@@ -95,6 +99,7 @@ def main():
     heal = [x for x in per_round if x["stage"] == "heal"]
     out = {
         "config": "BASELINE config 5",
+        "loss": args.loss,
         "workload": f"N={n} K={K} F={args.fanout} warm, 5% writes (1% deletes), tombstone grace 10 rounds, "
                     f"mtu 65507, partition into halves for rounds [{args.warm}, {args.warm + args.partition}) "
                     f"then heal for {args.heal} rounds",
