@@ -93,6 +93,7 @@ EXPORTS = [
     "gs_check_heartbeat_lag", "gs_stream_copy", "gs_stream_read", "gs_stream_write", "gs_set_timing", "gs_kernel_times",
     "gs_phase_overflow", "gs_phase_chain", "gs_phase_pending", "gs_comm_id", "gs_comm_init", "gs_run_phase_group", "gs_read_rows",
     "gs_latest_tick", "gs_flush_reports", "gs_set_ring_rows", "gs_mark", "gs_view_census", "gs_run_phase_cut", "gs_draw_cuts",
+    "gs_detect_census",
 ]
 
 API_VERSION = 23
@@ -162,6 +163,26 @@ class GsProbe(C.Structure):
 class GsViewTotals(C.Structure):
     _fields_ = ([(n, C.c_uint64) for n in VIEW_TOTAL_FIELDS] + [(n, C.c_uint64 * GS_VC_BUCKETS) for n in VIEW_HIST_FIELDS]
                 + [("reserved", C.c_uint64 * 9)])
+
+
+# gs_detect_census (include/gossip_sim.h)
+GS_DC_BUCKETS = 20
+GS_DC_MAX_THRESHOLDS = 16
+DETECT_TOTAL_FIELDS = [
+    "observers", "up_pairs", "up_live", "up_dead", "up_unknown", "down_pairs", "down_live", "down_dead", "down_unknown",
+    "up_windows", "down_windows", "up_phi", "down_phi", "old_windows", "early_deaths",
+    "max_detect_latency", "max_undetected_age", "max_false_age",
+]
+DETECT_MAX_FIELDS = ("max_detect_latency", "max_undetected_age", "max_false_age")  # maxima over the slices, not sums
+DETECT_HIST_FIELDS = ["detect_latency_hist", "undetected_age_hist", "false_age_hist"]
+DETECT_OVER_FIELDS = ["up_over", "down_over"]
+
+
+class GsDetectTotals(C.Structure):
+    _fields_ = ([(n, C.c_uint64) for n in DETECT_TOTAL_FIELDS]
+                + [(n, C.c_uint64 * GS_DC_BUCKETS) for n in DETECT_HIST_FIELDS]
+                + [(n, C.c_uint64 * GS_DC_MAX_THRESHOLDS) for n in DETECT_OVER_FIELDS]
+                + [("reserved", C.c_uint64 * 10)])
 
 
 class GsWire(C.Structure):
@@ -254,6 +275,7 @@ def load():
         "gs_materialize_held": (C.c_int, [P, u32, u32]),
         "gs_fd_census": (C.c_int, [P, P, C.POINTER(GsCensus)]),
         "gs_view_census": (C.c_int, [P, P, u32, C.POINTER(GsProbe), u32, C.POINTER(u64), P, P, C.POINTER(GsViewTotals)]),
+        "gs_detect_census": (C.c_int, [P, P, P, u32, C.POINTER(C.c_double), u32, P, P, C.POINTER(GsDetectTotals)]),
         "gs_set_events": (C.c_int, [P, P, u32, P]),
         "gs_select_peers": (C.c_int, [P, P, u32, P, u32, C.c_uint64, u32, P, P]),
         "gs_schedule_phases": (C.c_int, [P, P, u32, P, C.c_uint64, u32, u32, u32, P, P, P, C.POINTER(u32),

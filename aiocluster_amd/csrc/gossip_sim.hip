@@ -4776,6 +4776,316 @@ __global__ __launch_bounds__(LB, 4) void k_view_census(Dev d, VcArgs a, uint32_t
             if (s_rows[i]) atomicAdd(&a.rows[o0 + i], s_rows[i]);
 }
 
+// Detection census (gs_detect_census): a read-only streaming pass over GS_R_FD_STATE -- and, with thresholds (PHI),
+// over GS_R_FD_LAST and GS_R_FD -- that counts, over the pairs (observer o up, target j != o), the live / dead /
+// unknown pairs by whether the target is up, the detection latencies (time of death - down_since), the ages of
+// the undetected failures and of the false suspicions, and the pairs whose phi exceeds each swept threshold.
+// k_view_census's access pattern: one workgroup per (band of DC_BAND observer rows, chunk of LB x 16 columns), one
+// 16-byte non-temporal load of the state bytes per thread and row, rows in flight ahead of the one being reduced;
+// rows of down observers are neither loaded nor reduced (a wave-uniform choice).  The chunk's up bytes become two
+// byte masks per word (held in registers), down_since lives in LDS.
+// State only: four pairs per 32-bit word -- live and dead bytes by two bit operations, masked by the targets'
+// validity, accumulated in byte counters (widened every 128 rows).  The totals and the undetected ages follow from
+// the per-column counts at the end of the band (the age depends on the column alone).  Dead pairs go one at a time:
+// their time of death is loaded, bucketed into the workgroup's LDS histogram and folded into the column's
+// smallest / largest time of death.
+// PHI: per pair with a window, phi first in binary32 and division-free (numerator against threshold x denominator);
+// a value clear of every threshold by 2^-10 relative (the binary32 error is below 2^-20) counts for all or none of
+// them, any other is recomputed with k_phi_row's binary64
+// expression and compared with each threshold.  All results are integer sums, minima and maxima.
+constexpr uint32_t DC_BAND = 256;
+enum DcSlot {
+    DC_OBS = 0, DC_UP_PAIRS, DC_UP_LIVE, DC_UP_DEAD, DC_DN_PAIRS, DC_DN_LIVE, DC_DN_DEAD, DC_UP_WIN, DC_DN_WIN,
+    DC_UP_PHI, DC_DN_PHI, DC_OLD, DC_EARLY, DC_MAX /* latency, undetected age, false age */, DC_HIST = DC_MAX + 3,
+    DC_OVER = DC_HIST + 3 * GS_DC_BUCKETS, DC_NUM = DC_OVER + 2 * GS_DC_MAX_THRESHOLDS
+};
+struct DcArgs {
+    const uint8_t *up;
+    const uint32_t *down_since;  // nullptr: no latency / undetected-age histograms
+    uint32_t tick, tdec;         // tdec = the handle's latest tick: GS_R_FD_LAST decodes exactly against it
+    uint32_t n_thr;
+    float lo_all, hi_all;        // binary32 phi below lo_all: over no threshold; above hi_all: over every one
+    double thr[GS_DC_MAX_THRESHOLDS];
+    unsigned long long *acc;     // [DC_NUM], zeroed
+    uint32_t *targets, *rows;    // optional outputs: planes 0, 1, 3 zeroed, plane 2 GS_NONE; rows zeroed
+};
+__device__ __forceinline__ uint32_t dc_bucket(uint32_t x) { return min(GS_DC_BUCKETS - 1u, 32u - (uint32_t)__clz(x)); }
+// PHI holds 28 registers per row in flight: it is compiled for 2 workgroups per SIMD set (8 waves per CU x 2 rows x
+// 112 B per lane in flight), the state-only pass for 4 as k_view_census
+template <bool PHI>
+__global__ __launch_bounds__(LB, PHI ? 2 : 4) void k_detect_census(Dev d, DcArgs a, uint32_t chunks) {
+    constexpr uint32_t AHEAD = PHI ? 2u : 3u;  // rows in flight per thread (PHI: 112 B per row and lane)
+    __shared__ uint32_t s_hist[3][GS_DC_BUCKETS];
+    __shared__ uint32_t s_over[2][GS_DC_MAX_THRESHOLDS];
+    __shared__ uint32_t s_rows[DC_BAND];  // up targets held dead | down targets held live << 16
+    __shared__ uint32_t s_ds[16][LB];     // down_since of this thread's columns (read back by this thread only)
+    __shared__ double s_thr[GS_DC_MAX_THRESHOLDS];  // read on the binary64 path only
+    __shared__ uint32_t s_list[DC_BAND];  // the band's counted rows (up[o] != 0), in order: the loop runs over these
+    __shared__ uint32_t s_wc[LB / WAVE];
+    static_assert(DC_BAND == LB, "one thread per row of the band lists the counted rows");
+    const uint32_t tid = threadIdx.x;
+    const uint32_t rb = blockIdx.x / chunks, cb = blockIdx.x % chunks;
+    const uint32_t j0 = (cb * LB + tid) * 16u;
+    if (PHI && tid < GS_DC_MAX_THRESHOLDS) s_thr[tid] = a.thr[tid];
+    const uint32_t o0 = rb * DC_BAND, nrow = min(DC_BAND, d.N - o0);
+    const bool act = j0 < d.ncol;
+    const uint32_t nvt = act ? min(d.ncol - j0, 16u) : 0u;  // this thread's real columns (padding is never counted)
+    for (uint32_t i = tid; i < 3u * GS_DC_BUCKETS; i += LB) (&s_hist[0][0])[i] = 0u;
+    for (uint32_t i = tid; i < 2u * GS_DC_MAX_THRESHOLDS; i += LB) (&s_over[0][0])[i] = 0u;
+    s_rows[tid] = 0u;
+    // rows of down observers are neither loaded nor reduced: every load of the loop below is unconditional, so the
+    // compiler's wait for a row leaves the later rows in flight
+    const bool cnt_row = tid < nrow && a.up[o0 + tid];
+    const unsigned long long cnt_b = __ballot(cnt_row);
+    if ((tid & 63u) == 0u) s_wc[tid >> 6] = (uint32_t)__popcll(cnt_b);
+    // the targets' truth: byte masks of the up and the down columns, four columns per word
+    uint32_t upm[4] = {0u, 0u, 0u, 0u}, dnm[4] = {0u, 0u, 0u, 0u};
+    uint32_t upcnt = 0, dncnt = 0;
+#pragma unroll
+    for (uint32_t k = 0; k < 16u; k++) {
+        uint32_t ds = 0u;
+        if (k < nvt) {
+            const uint32_t j = d.col_lo + j0 + k;
+            if (a.up[j]) {
+                upm[k >> 2] |= 1u << (8u * (k & 3u));
+                upcnt++;
+            } else {
+                dnm[k >> 2] |= 1u << (8u * (k & 3u));
+                dncnt++;
+                if (a.down_since) ds = a.down_since[j];
+            }
+        }
+        s_ds[k][tid] = ds;
+    }
+    __syncthreads();
+    uint32_t nlist = 0;
+    {
+        uint32_t base = 0;
+#pragma unroll
+        for (uint32_t w = 0; w < LB / WAVE; w++) {
+            if (w < (tid >> 6)) base += s_wc[w];
+            nlist += s_wc[w];
+        }
+        if (cnt_row) s_list[base + (uint32_t)__popcll(cnt_b & ((1ull << (tid & 63u)) - 1ull))] = tid;
+    }
+    __syncthreads();
+    nlist = __builtin_amdgcn_readfirstlane(nlist);
+    const uint32_t jc = act ? j0 : 0u;  // a thread past the last column loads column 0's bytes: its masks are empty
+    struct Row {
+        v4u_t s;
+        v4u_t l[PHI ? 2 : 1], f[PHI ? 4 : 1];
+    };
+    Row buf[AHEAD];
+    auto row_of = [&](uint32_t i) { return o0 + (uint32_t)__builtin_amdgcn_readfirstlane(s_list[i]); };
+    auto ldv = [&](uint32_t i, Row &r) {
+        const size_t p0 = pix(d, row_of(i), jc);
+        r.s = __builtin_nontemporal_load(reinterpret_cast<const v4u_t *>(d.fd_state + p0));
+        if constexpr (PHI) {
+#pragma unroll
+            for (uint32_t i = 0; i < 2u; i++)
+                r.l[i] = __builtin_nontemporal_load(reinterpret_cast<const v4u_t *>(d.fd_last + p0) + i);
+#pragma unroll
+            for (uint32_t i = 0; i < 4u; i++)
+                r.f[i] = __builtin_nontemporal_load(reinterpret_cast<const v4u_t *>(d.fd + p0) + i);
+        }
+    };
+#pragma unroll
+    for (uint32_t u = 0; u < AHEAD; u++)
+        if (nlist) ldv(min(u, nlist - 1u), buf[u]);
+    // per target column over the band: live / dead counts as bytes (widened to 16-bit pairs every 128 rows, as
+    // k_view_census's beh), smallest and largest time of death
+    uint32_t lv8[4] = {0u, 0u, 0u, 0u}, dd8[4] = {0u, 0u, 0u, 0u}, lv16[8], dd16[8], tmin[16], tmax[16];
+#pragma unroll
+    for (uint32_t k = 0; k < 8u; k++) lv16[k] = dd16[k] = 0u;
+#pragma unroll
+    for (uint32_t k = 0; k < 16u; k++) { tmin[k] = NONE; tmax[k] = 0u; }
+    const uint32_t n_obs = nlist;
+    uint32_t n_diag = 0, t_early = 0, t_maxlat = 0, t_maxfalse = 0;
+    uint32_t t_upwin = 0, t_dnwin = 0, t_upphi = 0, t_dnphi = 0, t_old = 0, t_upall = 0, t_dnall = 0;
+    const uint32_t sum_mask = (1u << d.sum_bits) - 1u;
+    auto row = [&](uint32_t r, const Row &rw) {
+        const uint32_t o = row_of(r);
+        {
+            uint32_t rowc = 0;
+            if (act) {
+                uint32_t sw[4] = {rw.s.x, rw.s.y, rw.s.z, rw.s.w};
+                const uint32_t dj = o - (d.col_lo + j0);  // the diagonal pair is not counted (wraps when o is below)
+                if (dj < nvt) {
+                    n_diag++;
+#pragma unroll
+                    for (uint32_t q = 0; q < 4u; q++)
+                        if ((dj >> 2) == q) sw[q] &= ~(0xFFu << (8u * (dj & 3u)));
+                }
+#pragma unroll
+                for (uint32_t q = 0; q < 4u; q++) {
+                    const uint32_t x = sw[q], vm = upm[q] | dnm[q];
+                    const uint32_t lv = x & ~(x >> 1) & vm, dd = (x >> 1) & ~x & vm;
+                    lv8[q] += lv;
+                    dd8[q] += dd;
+                    rowc += (uint32_t)__popc(dd & upm[q]) | ((uint32_t)__popc(lv & dnm[q]) << 16);
+                    if (dd) {  // dead pairs, one at a time: the time of death
+#pragma unroll
+                        for (uint32_t i = 0; i < 4u; i++) {
+                            if (!((dd >> (8u * i)) & 1u)) continue;
+                            const uint32_t k = 4u * q + i;
+                            const uint32_t tod = d.tod[pix(d, o, j0 + k)];
+                            tmin[k] = min(tmin[k], tod);
+                            tmax[k] = max(tmax[k], tod);
+                            if ((upm[q] >> (8u * i)) & 1u) {  // a false suspicion: how long it has lasted
+                                const uint32_t age = a.tick - tod;
+                                t_maxfalse = max(t_maxfalse, age);
+                                atomicAdd(&s_hist[2][dc_bucket(age)], 1u);
+                            } else if (a.down_since) {
+                                const uint32_t ds = s_ds[k][tid];
+                                if (tod >= ds) {
+                                    t_maxlat = max(t_maxlat, tod - ds);
+                                    atomicAdd(&s_hist[0][dc_bucket(tod - ds)], 1u);
+                                } else {
+                                    t_early++;
+                                }
+                            }
+                        }
+                    }
+                }
+                if constexpr (PHI) {
+                    const uint32_t lw[8] = {rw.l[0].x, rw.l[0].y, rw.l[0].z, rw.l[0].w, rw.l[1].x, rw.l[1].y, rw.l[1].z, rw.l[1].w};
+                    const uint32_t fw[16] = {rw.f[0].x, rw.f[0].y, rw.f[0].z, rw.f[0].w, rw.f[1].x, rw.f[1].y, rw.f[1].z, rw.f[1].w,
+                                             rw.f[2].x, rw.f[2].y, rw.f[2].z, rw.f[2].w, rw.f[3].x, rw.f[3].y, rw.f[3].z, rw.f[3].w};
+#pragma unroll
+                    for (uint32_t k = 0; k < 16u; k++) {
+                        const uint32_t q = k >> 2, sh = 8u * (k & 3u);
+                        const uint32_t st = (sw[q] >> sh) & 0xFFu;
+                        const bool isup = (upm[q] >> sh) & 1u;
+                        if (!(st & FD_WIN) || !(((upm[q] | dnm[q]) >> sh) & 1u)) continue;
+                        if (isup) t_upwin++; else t_dnwin++;
+                        const uint32_t sum = fw[k] & sum_mask, cnt = fw[k] >> d.sum_bits;
+                        const uint32_t len = min(cnt, d.W);
+                        if (!len) continue;  // phi is None
+                        if (isup) t_upphi++; else t_dnphi++;
+                        const uint32_t l16 = (lw[k >> 1] >> (16u * (k & 1u))) & 0xFFFFu;
+                        // the report's age at tick, through the handle's latest tick (exact there: fd_get); a window
+                        // 2^15 ticks old or more is old, and decodes as tick - 2^15
+                        uint32_t age = (a.tick - a.tdec) + ((a.tdec - l16) & 0xFFFFu);
+                        if ((st & FD_OLD) || age >= FD_OLD_AGE) {
+                            age = FD_OLD_AGE;
+                            t_old++;
+                        }
+                        // phi = age (len + 5) / (sum + 5 prior), all in ticks: compared without dividing
+                        const float num = (float)age * ((float)len + 5.0f), den = (float)sum + d.prior5t_f;
+                        if (num < a.lo_all * den) continue;
+                        if (num > a.hi_all * den) {
+                            if (isup) t_upall++; else t_dnall++;
+                            continue;
+                        }
+                        const double mean = ((double)sum * TICK_S + d.prior5) / ((double)len + 5.0);
+                        const double phi = ((double)age * TICK_S) / mean;
+                        for (uint32_t i = 0; i < a.n_thr; i++)
+                            if (phi > s_thr[i]) atomicAdd(&s_over[isup ? 0 : 1][i], 1u);
+                    }
+                }
+            }
+            if (a.rows && __ballot(rowc != 0u)) {  // one wave reduction; one global atomic per (row, chunk, plane) below
+                const uint32_t s = wave_sum32(rowc);
+                if ((tid & 63u) == 0u && s) atomicAdd(&s_rows[o - o0], s);
+            }
+        }
+        if ((r & 127u) == 127u || r + 1u == nlist) {  // byte counters hold 128 rows: widen to 16-bit pairs
+#pragma unroll
+            for (uint32_t q = 0; q < 4u; q++) {
+                lv16[2u * q] += lv8[q] & 0x00FF00FFu;
+                lv16[2u * q + 1u] += (lv8[q] >> 8) & 0x00FF00FFu;
+                dd16[2u * q] += dd8[q] & 0x00FF00FFu;
+                dd16[2u * q + 1u] += (dd8[q] >> 8) & 0x00FF00FFu;
+                lv8[q] = dd8[q] = 0u;
+            }
+        }
+    };
+    for (uint32_t r0 = 0; r0 < nlist; r0 += AHEAD) {
+#pragma unroll
+        for (uint32_t u = 0; u < AHEAD; u++) {
+            const uint32_t r = r0 + u;
+            if (r >= nlist) break;
+            const Row rw = buf[u];
+            ldv(min(r + AHEAD, nlist - 1u), buf[u]);  // (past the list: the last row again, unused)
+            row(r, rw);
+        }
+    }
+    // the band's results: at most one atomic per (column, plane), zeros skipped; the totals and the undetected
+    // ages (tick - down_since of the column) from the per-column counts
+    uint32_t t_ul = 0, t_ud = 0, t_dl = 0, t_dd = 0, t_maxund = 0;
+#pragma unroll
+    for (uint32_t k = 0; k < 16u; k++) {
+        // column k = 4 q + i: counts in word 2 q + (i & 1), half i >> 1
+        const uint32_t w = 2u * (k >> 2) + (k & 1u), sh = 16u * ((k >> 1) & 1u);
+        const uint32_t lk = (lv16[w] >> sh) & 0xFFFFu, dk = (dd16[w] >> sh) & 0xFFFFu;
+        if (k >= nvt) continue;
+        if ((upm[k >> 2] >> (8u * (k & 3u))) & 1u) {
+            t_ul += lk;
+            t_ud += dk;
+        } else {
+            t_dl += lk;
+            t_dd += dk;
+            if (lk && a.down_since) {
+                const uint32_t ds = s_ds[k][tid], age = a.tick >= ds ? a.tick - ds : 0u;
+                t_maxund = max(t_maxund, age);
+                atomicAdd(&s_hist[1][dc_bucket(age)], lk);
+            }
+        }
+        if (!a.targets) continue;
+        if (lk) atomicAdd(&a.targets[j0 + k], lk);
+        if (dk) {
+            atomicAdd(&a.targets[d.ncol + j0 + k], dk);
+            atomicMin(&a.targets[2u * d.ncol + j0 + k], tmin[k]);
+            atomicMax(&a.targets[3u * d.ncol + j0 + k], tmax[k]);
+        }
+    }
+    {
+        const uint32_t lane0 = (tid & 63u) == 0u;
+        const uint32_t up_pairs = n_obs * upcnt - n_diag, dn_pairs = n_obs * dncnt;
+        const uint32_t v[12] = {up_pairs, t_ul, t_ud, dn_pairs, t_dl, t_dd, t_upwin, t_dnwin, t_upphi, t_dnphi, t_old, t_early};
+#pragma unroll
+        for (uint32_t i = 0; i < 12u; i++) {
+            if (!PHI && i >= 6u && i < 11u) continue;
+            const uint32_t s = wave_sum32(v[i]);
+            if (lane0 && s) atomicAdd(&a.acc[DC_UP_PAIRS + i], (unsigned long long)s);
+        }
+        const uint32_t m[3] = {wave_max32(t_maxlat), wave_max32(t_maxund), wave_max32(t_maxfalse)};
+#pragma unroll
+        for (uint32_t i = 0; i < 3u; i++)
+            if (lane0 && m[i]) atomicMax(&a.acc[DC_MAX + i], (unsigned long long)m[i]);
+        if constexpr (PHI) {  // the pairs above every threshold
+            const uint32_t su = wave_sum32(t_upall), sd = wave_sum32(t_dnall);
+            if (lane0)
+                for (uint32_t i = 0; i < a.n_thr; i++) {
+                    if (su) atomicAdd(&s_over[0][i], su);
+                    if (sd) atomicAdd(&s_over[1][i], sd);
+                }
+        }
+    }
+    if (cb == 0 && tid == 0 && n_obs) atomicAdd(&a.acc[DC_OBS], (unsigned long long)n_obs);
+    __syncthreads();
+    for (uint32_t i = tid; i < 3u * GS_DC_BUCKETS; i += LB) {
+        const uint32_t c = (&s_hist[0][0])[i];
+        if (c) atomicAdd(&a.acc[DC_HIST + i], (unsigned long long)c);
+    }
+    if (PHI)
+        for (uint32_t i = tid; i < 2u * GS_DC_MAX_THRESHOLDS; i += LB) {
+            const uint32_t c = (&s_over[0][0])[i];
+            if (c) atomicAdd(&a.acc[DC_OVER + i], (unsigned long long)c);
+        }
+    if (a.rows)
+        for (uint32_t i = tid; i < nrow; i += LB) {
+            const uint32_t c = s_rows[i];
+            if (c & 0xFFFFu) atomicAdd(&a.rows[o0 + i], c & 0xFFFFu);
+            if (c >> 16) atomicAdd(&a.rows[d.N + o0 + i], c >> 16);
+        }
+}
+// a target nobody holds dead has no largest time of death either (the plane was zeroed for atomicMax)
+__global__ __launch_bounds__(LB) void k_detect_fix(uint32_t *targets, uint32_t ncol) {
+    const uint32_t j = blockIdx.x * LB + threadIdx.x;
+    if (j < ncol && !targets[ncol + j]) targets[3u * ncol + j] = NONE;
+}
+
 // Escaped owner columns (gs_config.esc_cols), after a lag sweep: one workgroup decides the moves -- an escaped
 // column none of whose views is hot any more (every lag < HOT_HB) goes back to 8-bit views, a column the sweep
 // flagged (a view lagging by >= 2^7) takes a free slot (none free: counted in err_hb_lag) -- and marks every
@@ -5862,6 +6172,7 @@ struct gs_handle {
     uint16_t *sm_buf = nullptr;     // Dev::sm (one-slice prefix-view handles)
     unsigned long long *vc_buf = nullptr;  // gs_view_census scratch: VC_NUM u64 accumulators, then the probes
     std::vector<uint64_t> vc_img;          // ... and its host image (the upload before, the read after the pass)
+    unsigned long long *dc_buf = nullptr;  // gs_detect_census scratch: DC_NUM u64 accumulators
     hipStream_t hside = nullptr;    // k_pack_heavy's stream (forked after the lite slot work, joined after the packer)
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> tev[GS_KT_KINDS];
@@ -6475,6 +6786,7 @@ void gs_destroy(gs_handle *h) {
     if (h->heavy_buf) (void)hipFree(h->heavy_buf);
     if (h->sm_buf) (void)hipFree(h->sm_buf);
     if (h->vc_buf) (void)hipFree(h->vc_buf);
+    if (h->dc_buf) (void)hipFree(h->dc_buf);
     if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
     if (h->ev_join) (void)hipEventDestroy(h->ev_join);
     if (h->hside) (void)hipStreamDestroy(h->hside);
@@ -7666,6 +7978,97 @@ int gs_view_census(gs_handle *h, const uint8_t *up, uint32_t flags, const gs_pro
     out->version_lag_hist[0] = out->views - nzv;
     if (flags & GS_VC_HEARTBEATS) out->heartbeat_lag_hist[0] = out->views - nzh;
     for (uint32_t i = 0; i < n_probes; i++) reach[i] = acc[VC_REACH + i];
+    return GS_OK;
+}
+
+static_assert(sizeof(gs_detect_totals) == 120 * 8, "gs_detect_totals layout");
+
+int gs_detect_census(gs_handle *h, const uint8_t *up, const uint32_t *down_since, uint32_t tick, const double *thresholds,
+                     uint32_t n_thresholds, uint32_t *targets, uint32_t *rows, gs_detect_totals *out) {
+    if (!h) return GS_E_INVALID;
+    if (!up) return fail(h, GS_E_INVALID, "gs_detect_census: up is NULL");
+    if (!out) return fail(h, GS_E_INVALID, "gs_detect_census: out is NULL");
+    if (n_thresholds > GS_DC_MAX_THRESHOLDS)
+        return fail(h, GS_E_INVALID, "gs_detect_census: %u thresholds (at most %u)", n_thresholds, GS_DC_MAX_THRESHOLDS);
+    if (n_thresholds && !thresholds) return fail(h, GS_E_INVALID, "gs_detect_census: thresholds is NULL");
+    // gs_create's bound on phi_threshold, for every swept threshold: a window silent for >= 2^15 ticks is above it
+    const double widest = std::max((double)h->cfg.max_interval_ticks, h->cfg.prior_weighted / 5.0 * 64.0);
+    double tmin = 0.0, tmax = 0.0;
+    for (uint32_t i = 0; i < n_thresholds; i++) {
+        const double x = thresholds[i];
+        if (!(x >= 0.0) || !(x * widest < (double)FD_OLD_AGE))
+            return fail(h, GS_E_INVALID, "gs_detect_census: threshold %u = %g is NaN, negative or too large "
+                        "(threshold x max(max_interval, prior) must stay below 2^15 ticks)", i, x);
+        tmin = i ? std::min(tmin, x) : x;
+        tmax = i ? std::max(tmax, x) : x;
+    }
+    if ((int32_t)(tick - h->max_tick) < 0 || tick - h->max_tick >= FD_OLD_AGE)
+        return fail(h, GS_E_INVALID, "gs_detect_census: tick %u is before the handle's latest tick %u, or 2^15 or more "
+                    "past it", tick, h->max_tick);
+    if (!h->booted) return fail(h, GS_E_INVALID, "gs_detect_census: not booted");
+    if (!h->dc_buf) HIPCHK(h, hipMalloc(&h->dc_buf, (size_t)DC_NUM * 8));
+    hipStream_t s = h->stream;
+    HIPCHK(h, hipMemsetAsync(h->dc_buf, 0, (size_t)DC_NUM * 8, s));
+    if (targets) {
+        HIPCHK(h, hipMemsetAsync(targets, 0, (size_t)4 * h->ncol * 4, s));
+        HIPCHK(h, hipMemsetAsync(targets + (size_t)2 * h->ncol, 0xFF, (size_t)h->ncol * 4, s));
+    }
+    if (rows) HIPCHK(h, hipMemsetAsync(rows, 0, (size_t)2 * h->N * 4, s));
+    DcArgs a;
+    a.up = up;
+    a.down_since = down_since;
+    a.tick = tick;
+    a.tdec = h->max_tick;
+    a.n_thr = n_thresholds;
+    // binary32 phi carries a relative error below 2^-20: 2^-10 clear of every threshold decides all of them
+    a.lo_all = (float)(tmin * (1.0 - 0x1p-10));
+    a.hi_all = (float)(tmax * (1.0 + 0x1p-10));
+    for (uint32_t i = 0; i < GS_DC_MAX_THRESHOLDS; i++) a.thr[i] = i < n_thresholds ? thresholds[i] : 0.0;
+    a.acc = h->dc_buf;
+    a.targets = targets;
+    a.rows = rows;
+    const uint32_t chunks = (h->ncol + LB * 16 - 1) / (LB * 16);
+    const uint32_t grid = (h->N + DC_BAND - 1) / DC_BAND * chunks;
+    if (n_thresholds)
+        k_detect_census<true><<<grid, LB, 0, s>>>(h->d, a, chunks);
+    else
+        k_detect_census<false><<<grid, LB, 0, s>>>(h->d, a, chunks);
+    HIPCHK(h, hipGetLastError());
+    if (targets) {
+        k_detect_fix<<<(h->ncol + LB - 1) / LB, LB, 0, s>>>(targets, h->ncol);
+        HIPCHK(h, hipGetLastError());
+    }
+    uint64_t acc[DC_NUM];
+    HIPCHK(h, hipMemcpyAsync(acc, h->dc_buf, sizeof acc, hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipStreamSynchronize(s));
+    memset(out, 0, sizeof *out);
+    out->observers = acc[DC_OBS];
+    out->up_pairs = acc[DC_UP_PAIRS];
+    out->up_live = acc[DC_UP_LIVE];
+    out->up_dead = acc[DC_UP_DEAD];
+    out->up_unknown = out->up_pairs - out->up_live - out->up_dead;
+    out->down_pairs = acc[DC_DN_PAIRS];
+    out->down_live = acc[DC_DN_LIVE];
+    out->down_dead = acc[DC_DN_DEAD];
+    out->down_unknown = out->down_pairs - out->down_live - out->down_dead;
+    out->up_windows = acc[DC_UP_WIN];
+    out->down_windows = acc[DC_DN_WIN];
+    out->up_phi = acc[DC_UP_PHI];
+    out->down_phi = acc[DC_DN_PHI];
+    out->old_windows = acc[DC_OLD];
+    out->early_deaths = acc[DC_EARLY];
+    out->max_detect_latency = acc[DC_MAX];
+    out->max_undetected_age = acc[DC_MAX + 1];
+    out->max_false_age = acc[DC_MAX + 2];
+    for (uint32_t b = 0; b < GS_DC_BUCKETS; b++) {
+        out->detect_latency_hist[b] = acc[DC_HIST + b];
+        out->undetected_age_hist[b] = acc[DC_HIST + GS_DC_BUCKETS + b];
+        out->false_age_hist[b] = acc[DC_HIST + 2 * GS_DC_BUCKETS + b];
+    }
+    for (uint32_t i = 0; i < n_thresholds; i++) {
+        out->up_over[i] = acc[DC_OVER + i];
+        out->down_over[i] = acc[DC_OVER + GS_DC_MAX_THRESHOLDS + i];
+    }
     return GS_OK;
 }
 

@@ -402,6 +402,62 @@ class ShardGroup:
             out["row_stale"] = t
         return out
 
+    def detect_census(self, up, tick: int | None = None, down_since=None, thresholds=(), per_target: bool = False,
+                      per_row: bool = False) -> dict:
+        """``GossipSim.detect_census`` of the whole cluster: totals, histograms, ``up_over`` / ``down_over`` and
+        the per-row counts summed over the slices (``observers`` taken once), maxima maxed, the per-target tensors
+        joined along the target axis (each slice holds its own targets, so the smallest and largest times of death
+        need no combining).  Over a ``DistComm`` the sums and maxima are all-reduced and the per-target parts
+        gathered, as ``view_census`` does."""
+        import torch
+
+        from ._lib import DETECT_HIST_FIELDS, DETECT_MAX_FIELDS, DETECT_OVER_FIELDS, DETECT_TOTAL_FIELDS
+        from .detect import detect_rates
+
+        thresholds = list(thresholds)
+        parts = [s.detect_census(up, tick, down_since, thresholds, per_target, per_row) for s in self.slices]
+        sums = [k for k in DETECT_TOTAL_FIELDS if k not in DETECT_MAX_FIELDS and k != "observers"]
+        lists = DETECT_HIST_FIELDS + DETECT_OVER_FIELDS
+        vec = [sum(p[k] for p in parts) for k in sums]
+        for k in lists:
+            vec += [sum(p[k][b] for p in parts) for b in range(len(parts[0][k]))]
+        mx = [max(p[k] for p in parts) for k in DETECT_MAX_FIELDS]
+        dist = isinstance(self.comm, DistComm)
+        dev = self.slices[0].device
+        if dist:
+            d = self.comm.dist
+            cdev = "cpu" if d.get_backend(self.comm.group) == "gloo" else dev
+            v = torch.tensor(vec, dtype=torch.int64, device=cdev)
+            m = torch.tensor(mx, dtype=torch.int64, device=cdev)
+            d.all_reduce(v, group=self.comm.group)
+            d.all_reduce(m, op=d.ReduceOp.MAX, group=self.comm.group)
+            vec, mx = [int(x) for x in v.tolist()], [int(x) for x in m.tolist()]
+        out = {"observers": parts[0]["observers"]}
+        it = iter(vec)
+        out.update((k, next(it)) for k in sums)
+        out.update(zip(DETECT_MAX_FIELDS, mx))
+        out = {k: out[k] for k in DETECT_TOTAL_FIELDS}
+        for k in lists:
+            out[k] = [next(it) for _ in parts[0][k]]
+        out.update(detect_rates(out))
+        if per_target:
+            for k in ("target_live_by", "target_dead_by", "target_first_tod", "target_last_tod"):
+                t = torch.cat([p[k] for p in parts])
+                if dist:  # slices differ in width (the last one is shorter): gathered padded to the widest
+                    blk = _slice_block(self.n, self.comm.world)
+                    pad = torch.zeros(blk, dtype=t.dtype, device=t.device)
+                    pad[: t.numel()] = t
+                    allp = self.comm.gather([pad])
+                    t = torch.cat([allp[g, : min(blk, self.n - g * blk)] for g in range(self.comm.world)])
+                out[k] = t
+        if per_row:
+            for k in ("row_false_suspicions", "row_undetected"):
+                t = torch.stack([p[k] for p in parts]).sum(0, dtype=torch.int32)
+                if dist:
+                    t = self.comm.gather([t]).sum(0, dtype=torch.int32)
+                out[k] = t
+        return out
+
     def export(self) -> dict:
         """The slices this process holds, joined along the owner axis (all of them in-process)."""
         parts = [s.export() for s in self.slices]

@@ -36,6 +36,7 @@ import numpy as np
 from . import _lib
 from ._lib import (GS_CANONICAL, GS_FD_RING, GS_HB8, GS_MV8, GS_NO_HELD, GS_NONE, GS_SLICED, GS_TOMBSTONES, REGION,
                    TICK_US, GsError)
+from .detect import detect_rates
 from .entities import ClusterSnapshot, NodeId, NodeState, VersionedValue, VersionStatusEnum
 from .pbsize import nodeid_size
 
@@ -617,6 +618,55 @@ class GossipSim:
             out["owner_behind"], out["owner_unknown"], out["owner_max_lag"] = owners[0], owners[1], owners[2]
         if per_row:
             out["row_stale"] = rows
+        return out
+
+    def detect_census(self, up, tick: int | None = None, down_since=None, thresholds=(), per_target: bool = False,
+                      per_row: bool = False) -> dict:
+        """gs_detect_census: what the failure detector makes of the cluster against the truth ``up``, in one
+        read-only device pass (blocking).  Over the pairs (observer up, target != observer) of this handle's
+        columns: ``up_pairs`` / ``up_live`` / ``up_dead`` / ``up_unknown`` and the same for down targets;
+        with ``down_since`` (``detect.DownClock.down_since``: the tick each down node went down)
+        ``detect_latency_hist`` (time of death - down_since), ``undetected_age_hist`` (tick - down_since of the
+        pairs still held live) and ``early_deaths``; ``false_age_hist`` (tick - time of death of up targets held
+        dead); the maxima of the three; 20 buckets in ticks (0, then 2^(b-1) <= x < 2^b).  With ``thresholds``
+        (at most 16) the pass also reads the windows: ``up_windows`` / ``up_phi`` / ``old_windows`` and
+        ``up_over[i]`` / ``down_over[i]`` = the pairs whose phi at ``tick`` (default: the last liveness tick)
+        exceeds ``thresholds[i]``.  Derived: ``false_suspicion_rate`` = up_dead / up_pairs, ``detected_fraction``
+        = down_dead / down_pairs, ``undetected`` = down_live.  ``per_target`` adds the device int32 tensors
+        ``target_live_by``, ``target_dead_by``, ``target_first_tod``, ``target_last_tod`` ([ncol]; -1 = nobody holds
+        it dead); ``per_row`` adds ``row_false_suspicions`` and ``row_undetected`` ([N])."""
+        self._flush()
+        if "gs_detect_census" in self.L.gs_missing:
+            raise GsError("gs_detect_census: this GS_LIB build lacks the entry point")
+        torch = self.torch
+        u = up if hasattr(up, "data_ptr") else self._dev(np.asarray(up, dtype=np.uint8), torch.uint8)
+        ds = None
+        if down_since is not None:
+            ds = (down_since if hasattr(down_since, "data_ptr")
+                  else self._dev(np.asarray(down_since, dtype=np.uint32).view(np.int32), torch.int32))
+        thr = [float(x) for x in thresholds]
+        n = len(thr)
+        ta = (C.c_double * max(n, 1))(*thr)
+        targets = torch.empty((4, self.ncol), dtype=torch.int32, device=self.device) if per_target else None
+        rows = torch.empty((2, self.n), dtype=torch.int32, device=self.device) if per_row else None
+        tot = _lib.GsDetectTotals()
+        self._chk(self.L.gs_detect_census(self.h, C.c_void_p(u.data_ptr()),
+                                          C.c_void_p(ds.data_ptr()) if ds is not None else None,
+                                          self.last_tick if tick is None else int(tick), ta if n else None, n,
+                                          C.c_void_p(targets.data_ptr()) if per_target else None,
+                                          C.c_void_p(rows.data_ptr()) if per_row else None, C.byref(tot)),
+                  "gs_detect_census")
+        out = {k: int(getattr(tot, k)) for k in _lib.DETECT_TOTAL_FIELDS}
+        for k in _lib.DETECT_HIST_FIELDS:
+            out[k] = [int(x) for x in getattr(tot, k)]
+        for k in _lib.DETECT_OVER_FIELDS:
+            out[k] = [int(x) for x in getattr(tot, k)][:n]
+        out.update(detect_rates(out))
+        if per_target:
+            (out["target_live_by"], out["target_dead_by"], out["target_first_tod"],
+             out["target_last_tod"]) = targets[0], targets[1], targets[2], targets[3]
+        if per_row:
+            out["row_false_suspicions"], out["row_undetected"] = rows[0], rows[1]
         return out
 
     def reach(self, owner: int, version: int | None = None, up=None) -> int:

@@ -510,6 +510,60 @@ int gs_view_census(gs_handle *h, const uint8_t *up /*DEVICE or NULL*/, uint32_t 
                    uint32_t *rows /*DEVICE [N] or NULL: per observer, this handle's owner columns it is behind on or does not know; 0 for rows not counted*/,
                    gs_view_totals *out /*HOST*/);
 
+/* Detection census: what the failure detector makes of the cluster, against the caller's ground truth.  One
+ * read-only streaming pass over GS_R_FD_STATE (GS_R_FD_TOD for the dead pairs; with thresholds also GS_R_FD_LAST and
+ * GS_R_FD).  It stands in for FailureDetector.live_nodes / dead_nodes / phi of every observer
+ * (failure_detector.py:60-87).
+ *   Counted pairs: an observer o with up[o] != 0 (DEVICE u8 [N]) and a target column j of this handle with
+ *     col_lo + j != o.  The target's truth is up[col_lo + j]; its state is GS_R_FD_STATE & 3 (1 live, 2 dead,
+ *     0 unknown); the time of death `tod` of a dead pair is its GS_R_FD_TOD.  No dict-position region is read: a pair
+ *     the observer does not know, or has removed, is state 0.
+ *   down_since (DEVICE u32 [N] or NULL): down_since[j] = the tick at which down node j went down (entries of up
+ *     nodes are ignored).  NULL: detect_latency_hist, undetected_age_hist, their maxima and early_deaths are zero;
+ *     false_age_hist needs only `tick`.
+ *   phi: SamplingWindow.phi at `tick` with the binary64 expression of gs_phi_row -- the window's last report
+ *     decoded as gs_phi_row does (an old window as tick - 2^15), len = min(count, window), mean =
+ *     (sum / 64 + prior_weighted) / (len + 5), phi = ((tick - last) / 64) / mean -- compared as phi > thresholds[i] in
+ *     binary64 (a binary32 value decides only the pairs it is clear of every threshold by 2^-10 relative).  With
+ *     n_thresholds == 0 neither GS_R_FD nor GS_R_FD_LAST is read, and up_windows, down_windows, up_phi, down_phi and
+ *     old_windows are zero.  Reports still held in the round's planes (before the liveness sweep or
+ *     gs_flush_reports) are not in the windows yet, as for gs_phi_row.
+ *   targets (DEVICE u32 [4][n_cols] or NULL): per target column {counted observers holding it live, holding it dead,
+ *     smallest tod, largest tod}; both tod entries are GS_NONE when nobody holds it dead.  The smallest tod is the
+ *     first detection of a failed node, the largest the time by which every observer holding it dead had detected it.
+ *   rows (DEVICE u32 [2][N] or NULL): per observer {up targets it holds dead, down targets it still holds live} among
+ *     this handle's columns; 0 for rows not counted.
+ * Blocking; every output is overwritten; no region and no field of gs_read_counters changes (err_fd_overflow is not
+ * counted, unlike gs_phi_row: old windows are reported in old_windows, and every valid threshold is below their phi).
+ * Sliced handles count their own target columns: sums add over the slices, maxima take the largest, the smallest tod
+ * the smallest; observers is the same in every slice.
+ * GS_E_INVALID (checked before any device work; gs_last_error names gs_detect_census): h, up or out NULL;
+ * n_thresholds > GS_DC_MAX_THRESHOLDS; n_thresholds > 0 with thresholds NULL; a threshold that is NaN, negative or has
+ * threshold x max(max_interval, prior) >= 2^15 ticks (gs_create's bound on phi_threshold); tick below gs_latest_tick,
+ * or 2^15 or more past it. */
+#define GS_DC_BUCKETS 20u          /* ticks; bucket 0: 0; bucket b >= 1: 2^(b-1) <= x < 2^b; bucket 19 also takes x >= 2^19 (GS_VC_BUCKETS' rule) */
+#define GS_DC_MAX_THRESHOLDS 16u
+typedef struct gs_detect_totals {  /* all u64, 120 words */
+    uint64_t observers;                                   /* rows counted: up[o] != 0 */
+    uint64_t up_pairs, up_live, up_dead, up_unknown;      /* counted pairs (o up, j != o) whose target is up, by (GS_R_FD_STATE & 3): 1, 2, 0 */
+    uint64_t down_pairs, down_live, down_dead, down_unknown;
+    uint64_t up_windows, down_windows;                    /* pairs with a sampling window (a last report) */
+    uint64_t up_phi, down_phi;                            /* ... whose phi is not None: the window holds >= 1 interval */
+    uint64_t old_windows;                                 /* of up_phi + down_phi: old windows -- marked old in GS_R_FD_STATE, or last report >= 2^15 ticks before `tick` though not yet marked (gs_phi_row decodes the latter exactly; both are above every valid threshold) */
+    uint64_t early_deaths;                                /* down and dead pairs with tod < down_since[j] (suspected before the node went down); not in the latency histogram */
+    uint64_t max_detect_latency, max_undetected_age, max_false_age;   /* ticks */
+    uint64_t detect_latency_hist[GS_DC_BUCKETS];          /* down & dead, tod >= down_since[j]: tod - down_since[j] */
+    uint64_t undetected_age_hist[GS_DC_BUCKETS];          /* down & live: tick - down_since[j] */
+    uint64_t false_age_hist[GS_DC_BUCKETS];               /* up & dead: tick - tod (how long the false suspicion has lasted) */
+    uint64_t up_over[GS_DC_MAX_THRESHOLDS];               /* pairs counted in up_phi with phi > thresholds[i] */
+    uint64_t down_over[GS_DC_MAX_THRESHOLDS];             /* pairs counted in down_phi with phi > thresholds[i] */
+    uint64_t reserved[10];                                /* 18 fields + 3 x 20 + 2 x 16 + 10 = 120 words */
+} gs_detect_totals;
+int gs_detect_census(gs_handle *h, const uint8_t *up /*DEVICE [N]*/, const uint32_t *down_since /*DEVICE [N] or NULL*/,
+                     uint32_t tick, const double *thresholds /*HOST*/, uint32_t n_thresholds,
+                     uint32_t *targets /*DEVICE [4][ncol] or NULL*/, uint32_t *rows /*DEVICE [2][N] or NULL*/,
+                     gs_detect_totals *out /*HOST*/);
+
 /* Wire-format emitter: the protobuf bytes the reference's SerializeToString gives, from device state,
  * so a simulated cluster can talk to real aiocluster nodes (messages.proto:46-74).  String tables are
  * DEVICE arrays owned by the caller: NodeIdPb bytes of every node (entities.py:62-72; node i at
