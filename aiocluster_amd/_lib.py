@@ -93,7 +93,7 @@ EXPORTS = [
     "gs_check_heartbeat_lag", "gs_stream_copy", "gs_stream_read", "gs_stream_write", "gs_set_timing", "gs_kernel_times",
     "gs_phase_overflow", "gs_phase_chain", "gs_phase_pending", "gs_comm_id", "gs_comm_init", "gs_run_phase_group", "gs_read_rows",
     "gs_latest_tick", "gs_flush_reports", "gs_set_ring_rows", "gs_mark", "gs_view_census", "gs_run_phase_cut", "gs_draw_cuts",
-    "gs_detect_census",
+    "gs_detect_census", "gs_traffic_census",
 ]
 
 API_VERSION = 23
@@ -183,6 +183,22 @@ class GsDetectTotals(C.Structure):
                 + [(n, C.c_uint64 * GS_DC_BUCKETS) for n in DETECT_HIST_FIELDS]
                 + [(n, C.c_uint64 * GS_DC_MAX_THRESHOLDS) for n in DETECT_OVER_FIELDS]
                 + [("reserved", C.c_uint64 * 10)])
+
+
+# gs_traffic_census (include/gossip_sim.h)
+GS_TC_FRAME_LIMIT = 1
+GS_TC_BUCKETS = 32
+TRAFFIC_KINDS = ("syn", "synack", "ack")
+TRAFFIC_SCALAR_FIELDS = ["exchanges", "bad_index"]
+TRAFFIC_KIND_FIELDS = ["sent", "delivered", "lost", "rejected", "bytes_sent", "bytes_delivered"]  # [3]: by message kind
+TRAFFIC_BYTE_FIELDS = ["digest_bytes_sent", "delta_bytes_sent", "delta_bytes_delivered"]
+TRAFFIC_MAX_FIELDS = ("max_frame",)  # maxima, not sums
+
+
+class GsTrafficTotals(C.Structure):
+    _fields_ = ([(n, C.c_uint64) for n in TRAFFIC_SCALAR_FIELDS] + [(n, C.c_uint64 * 3) for n in TRAFFIC_KIND_FIELDS]
+                + [(n, C.c_uint64) for n in TRAFFIC_BYTE_FIELDS] + [("max_frame", C.c_uint64 * 3)]
+                + [("frame_hist", (C.c_uint64 * GS_TC_BUCKETS) * 3), ("reserved", C.c_uint64 * 6)])
 
 
 class GsWire(C.Structure):
@@ -276,6 +292,7 @@ def load():
         "gs_fd_census": (C.c_int, [P, P, C.POINTER(GsCensus)]),
         "gs_view_census": (C.c_int, [P, P, u32, C.POINTER(GsProbe), u32, C.POINTER(u64), P, P, C.POINTER(GsViewTotals)]),
         "gs_detect_census": (C.c_int, [P, P, P, u32, C.POINTER(C.c_double), u32, P, P, C.POINTER(GsDetectTotals)]),
+        "gs_traffic_census": (C.c_int, [P, P, P, P, u32, u32, u32, u32, P, P, P, C.POINTER(GsTrafficTotals)]),
         "gs_set_events": (C.c_int, [P, P, u32, P]),
         "gs_select_peers": (C.c_int, [P, P, u32, P, u32, C.c_uint64, u32, P, P]),
         "gs_schedule_phases": (C.c_int, [P, P, u32, P, C.c_uint64, u32, u32, u32, P, P, P, C.POINTER(u32),

@@ -795,7 +795,7 @@ __device__ __forceinline__ void pack_group(const Dev &d, uint32_t s, uint32_t r,
     if (tail && mtu - S < d.lb_min) stop = true;
     if (REC) {  // lanes hold candidates in sender order: rank by lane
         const unsigned long long sm = __ballot(vsel != 0u);
-        if (vsel) rec[nr + (uint32_t)__popcll(sm & ((1ull << lane) - 1ull))] = make_uint2(c.j, vsel);
+        if (vsel && rec) rec[nr + (uint32_t)__popcll(sm & ((1ull << lane) - 1ull))] = make_uint2(c.j, vsel);  // (no buffer: size only, k_traffic)
         nr += (uint32_t)__popcll(sm);
         return;
     }
@@ -1091,7 +1091,7 @@ __device__ __forceinline__ void pack_dir(const Dev &d, uint32_t s, uint32_t r, c
     pst.stop = stop;
     pst.m1 = m1;
     if (REC) {
-        if (lane == 0) *nrec = nr;
+        if (lane == 0 && nrec) *nrec = nr;
         return;
     }
     if (!COUNT && lane == 0) shard_add(d, C_DBYTES, S - S0);  // DeltaPb bytes this call added
@@ -5539,6 +5539,261 @@ __global__ __launch_bounds__(LB) void k_delta_write(Dev d, Wire w, uint32_t s, u
     put_var(p, c.ms);
 }
 
+// ------------------------------------------------------------------ traffic census
+// gs_traffic_census: what a phase would put on the wire, without running it.  One two-wave workgroup per
+// exchange a -> b.  Wave 0 sizes a's Syn digest and b's SynAck delta (direction b -> a), wave 1 b's SynAck
+// digest -- pass1_grp's merge rules restated without the stores: b's own heartbeat + 1, max(b's view, a's) for
+// the owners of a's digest, an owner b did not know entering with a's heartbeat -- and a's Ack delta
+// (direction a -> b, on a's pre-exchange views: DESIGN.md §4, the two deltas commute).  Each wave streams both
+// rows once, builds its direction's stale-owner bitmap in LDS as k_delta_plan does, and runs the packer in
+// record mode with no record buffer: nothing is applied, stored or counted, the DeltaPb size is PackState::S.
+// Thread 0 then forms the three packets (PacketPb around the bodies, server.py:327-370), decides which the
+// peer would refuse (_read_message, server.py:502-514) and adds the exchange to the totals.
+struct TcArgs {
+    const int32_t *ini, *res;
+    const uint8_t *legs;  // messages the network delivers per exchange (nullptr: 3)
+    uint32_t n, t, cid, flags;  // cid: UTF-8 bytes of the cluster id
+    uint32_t *msg;              // [n][4] or nullptr
+    uint8_t *legs_out;          // [n] or nullptr
+    unsigned long long *nodes;  // [2][N] or nullptr: wire bytes sent / accepted per node (added to)
+    unsigned long long *acc;    // [NSHARD][TC_NUM] or nullptr: gs_traffic_totals in word order, sharded
+};
+enum Tc {
+    TC_EXCH = 0, TC_BAD, TC_SENT = 2, TC_DELIV = 5, TC_LOST = 8, TC_REJ = 11, TC_BSENT = 14, TC_BDELIV = 17,
+    TC_DIG_SENT = 20, TC_DEL_SENT, TC_DEL_DELIV, TC_MAXF = 23, TC_HIST = 26, TC_NUM = 128
+};
+static_assert(TC_HIST + 3 * GS_TC_BUCKETS <= TC_NUM, "gs_traffic_totals words");
+
+// one DigestPb entry (state.py:56-58): NodeDigestPb {node_id, heartbeat, last_gc_version, max_version}
+__device__ __forceinline__ uint32_t tc_entry(uint32_t nid, uint32_t H, uint32_t G, uint32_t M) {
+    return msgf(msgf(nid) + ufield(H) + ufield(G) + ufield(M));
+}
+// One owner column j of exchange a -> b, for wave w1 (0: Syn digest + direction b -> a, 1: SynAck digest +
+// direction a -> b).  pa / pb: the row knows j; sa / sb: and has it scheduled for deletion; a view the row does
+// not hold comes in as zeros.  Returns the digest entry's bytes; stale = j is a stale owner of the direction.
+__device__ __forceinline__ uint32_t tc_col(bool w1, bool isb, bool pa, bool pb, bool sa, bool sb, uint32_t hA,
+                                           uint32_t hB, uint32_t gA, uint32_t gB, uint32_t mA, uint32_t mB,
+                                           uint32_t nid, bool &stale) {
+    const bool inA = pa && !sa;  // j is in a's digest (compute_digest, state.py:324-331)
+    if (!w1) {
+        stale = pb && !sb && mB > (inA ? mA : 0u);  // state.py:347-357
+        return inA ? tc_entry(nid, hA, gA, mA) : 0u;
+    }
+    // b's digest after its own inc_heartbeat (server.py:524) and _report_heartbeat over a's (server.py:334-340)
+    const bool mrg = inA && !isb;
+    const bool newB = mrg && !pb;  // node_state_or_default: heartbeat = a's view, last_gc 0, max_version 0
+    const bool inB = (pb || newB) && !sb;
+    uint32_t H = hB + (isb ? 1u : 0u);
+    if (mrg && (newB || hA > H)) H = hA;  // apply_heartbeat (state.py:280-287)
+    stale = pa && !sa && mA > (inB ? mB : 0u);
+    return inB ? tc_entry(nid, H, gB, mB) : 0u;
+}
+
+__device__ __forceinline__ uint32_t tc_bucket(uint32_t x) { return min(GS_TC_BUCKETS - 1u, 32u - (uint32_t)__clz(x)); }
+
+#ifndef TC_WAVES
+#define TC_WAVES 4  // waves per SIMD k_traffic<4, .> is compiled for (the packer's budget: PK_WAVES)
+#endif
+template <int KW, bool GENM>
+__global__ __launch_bounds__(XB, (KW == 4 ? TC_WAVES : 1)) void k_traffic(Dev d, TcArgs a) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
+    __shared__ uint32_t s_sz[4];  // msg[e]: Syn digest, SynAck digest, SynAck delta, Ack delta
+    const uint32_t e = blockIdx.x;
+    const int lane = lane_id();
+    const uint32_t w = threadIdx.x / WAVE;
+    const int32_t ai = a.ini[e], bi = a.res[e];
+    const uint32_t lg = a.legs ? a.legs[e] : 3u;
+    if (ai < 0 || bi < 0 || (uint32_t)ai >= d.N || (uint32_t)bi >= d.N || ai == bi || lg > 3u) {
+        if (threadIdx.x == 0) {  // counted in bad_index and nowhere else
+            if (a.msg)
+                for (uint32_t k = 0; k < 4u; k++) a.msg[(size_t)e * 4 + k] = 0u;
+            if (a.legs_out) a.legs_out[e] = 0;
+            if (a.acc) atomicAdd(&a.acc[(e % NSHARD) * TC_NUM + TC_BAD], 1ull);
+        }
+        return;
+    }
+    const uint32_t ua = (uint32_t)ai, ub = (uint32_t)bi, t = a.t;
+    const bool w1 = w != 0u;
+    const uint32_t wstride = WIN / 2 + d.NP / 32;  // u32 words per wave: wbuf, then the bitmap
+    uint16_t *wbuf = reinterpret_cast<uint16_t *>(lds + w * wstride);
+    uint32_t *bits = lds + w * wstride + WIN / 2;
+    const bool schA = t >= d.row[ua * 4 + 2], schB = t >= d.row[ub * 4 + 2];
+    const bool gct = (d.flags & GS_TOMBSTONES) != 0;
+    const size_t ra = (size_t)ua * d.NP, rb = (size_t)ub * d.NP;
+    uint32_t dig = 0;  // this lane's share of the wave's digest bytes
+    if (!GENM && !gct && !schA && !schB) {
+        // canonical rows, nothing scheduled: 16 bytes per lane, row and region per step (PER columns: 16 at 8-bit
+        // max_version views, else 8), the next step's loads issued before this one is reduced
+        const uint32_t PER = d.mv8 ? 16u : 8u, STEP = PER * WAVE;
+        const uint8_t *h8 = reinterpret_cast<const uint8_t *>(d.hb), *m8 = reinterpret_cast<const uint8_t *>(d.mv);
+        const uint32_t hsh = d.hb8 ? 0u : 1u, msh = d.mv8 ? 0u : 1u;  // log2 bytes per view
+        const bool hwide = (PER << hsh) == 16u;                         // heartbeats: 16 bytes per step, else 8
+        struct Raw { v4u_t mA, mB, hA, hB; };
+        auto ldh = [&](size_t p) {
+            if (hwide) return __builtin_nontemporal_load(reinterpret_cast<const v4u_t *>(h8 + (p << hsh)));
+            const v2u_t x = __builtin_nontemporal_load(reinterpret_cast<const v2u_t *>(h8 + (p << hsh)));
+            return v4u_t{x.x, x.y, 0u, 0u};
+        };
+        auto ld = [&](uint32_t c0, Raw &r) {
+            r.mA = r.mB = r.hA = r.hB = v4u_t{0u, 0u, 0u, 0u};
+            if (c0 >= d.NP) return;  // rows are NP = a multiple of 64 columns wide: a started group is in bounds
+            r.mA = __builtin_nontemporal_load(reinterpret_cast<const v4u_t *>(m8 + ((ra + c0) << msh)));
+            r.mB = __builtin_nontemporal_load(reinterpret_cast<const v4u_t *>(m8 + ((rb + c0) << msh)));
+            r.hA = ldh(ra + c0);
+            if (w1) r.hB = ldh(rb + c0);
+        };
+        // view k of a group of 8-bit (w8) or 16-bit views; k is a constant once the loops below are unrolled, so
+        // both words are picked by constant indices and the width only selects between them
+        auto view = [](const uint32_t (&v)[4], uint32_t w8, uint32_t k) {
+            const uint32_t b8 = (v[(k >> 2) & 3u] >> (8u * (k & 3u))) & 0xFFu;
+            const uint32_t b16 = (v[(k >> 1) & 3u] >> (16u * (k & 1u))) & 0xFFFFu;
+            return w8 ? b8 : b16;
+        };
+        Raw cur, nxt;
+        ld(PER * (uint32_t)lane, cur);
+        for (uint32_t s0 = 0; s0 < d.NP; s0 += STEP) {
+            const uint32_t c0 = s0 + PER * (uint32_t)lane;
+            ld(c0 + STEP, nxt);
+            uint32_t sm = 0u;  // bit i: column c0 + i is stale in this wave's direction
+            if (c0 < d.ncol) {
+                const uint32_t mAw[4] = {cur.mA.x, cur.mA.y, cur.mA.z, cur.mA.w};
+                const uint32_t mBw[4] = {cur.mB.x, cur.mB.y, cur.mB.z, cur.mB.w};
+                const uint32_t hAw[4] = {cur.hA.x, cur.hA.y, cur.hA.z, cur.hA.w};
+                const uint32_t hBw[4] = {cur.hB.x, cur.hB.y, cur.hB.z, cur.hB.w};
+#pragma unroll
+                for (uint32_t q = 0; q < 16u; q += 4u) {  // 4 columns: their owner-table entries in one round trip
+                    const uint32_t jq = c0 + q;
+                    if (q >= PER || jq >= d.ncol) continue;
+                    uint32_t R[4], M[4] = {0u, 0u, 0u, 0u}, es[4] = {NONE, NONE, NONE, NONE};
+                    ld4(d.self_hb + jq, R);
+                    if (d.mv8) ld4(d.self_mv + jq, M);
+                    if (d.EC) ld4(d.esc_slot + jq, es);
+                    const uint2 nz = *reinterpret_cast<const uint2 *>(d.nid_size + jq);
+                    const uint32_t nid[4] = {nz.x & 0xFFFFu, nz.x >> 16, nz.y & 0xFFFFu, nz.y >> 16};
+#pragma unroll
+                    for (uint32_t i = 0; i < 4u; i++) {
+                        const uint32_t j = jq + i, k = q + i;
+                        if (j >= d.ncol) continue;
+                        const uint32_t rmA = view(mAw, d.mv8, k), rmB = view(mBw, d.mv8, k);
+                        const uint32_t rhA = view(hAw, d.hb8, k), rhB = view(hBw, d.hb8, k);
+                        const uint32_t mA = (d.mv8 ? mv_dec8(rmA, M[i]) : rmA) & MV_MASK;
+                        const uint32_t mB = (d.mv8 ? mv_dec8(rmB, M[i]) : rmB) & MV_MASK;
+                        uint32_t hA, hB = 0u;
+                        if (es[i] != NONE) {  // an escaped column: its views are the 16-bit slots
+                            hA = hb_dec(d.esc16[(size_t)ua * d.EC + es[i]], R[i]);
+                            if (w1) hB = hb_dec(d.esc16[(size_t)ub * d.EC + es[i]], R[i]);
+                        } else {
+                            hA = d.hb8 ? hb_dec8(rhA, R[i]) : hb_dec(rhA, R[i]);
+                            if (w1) hB = d.hb8 ? hb_dec8(rhB, R[i]) : hb_dec(rhB, R[i]);
+                        }
+                        bool stale;
+                        dig += tc_col(w1, d.col_lo + j == ub, true, true, false, false, hA, hB, 0u, 0u, mA, mB, nid[i],
+                                      stale);
+                        sm |= (uint32_t)stale << k;
+                    }
+                }
+            }
+            if (c0 < d.NP) {  // this lane's bitmap bits (zeros past ncol); nothing past the row's NP / 32 words
+                if (d.mv8) reinterpret_cast<uint16_t *>(bits)[c0 >> 4] = (uint16_t)sm;
+                else reinterpret_cast<uint8_t *>(bits)[c0 >> 3] = (uint8_t)sm;
+            }
+            cur = nxt;
+        }
+    } else {
+        // the general and tombstone layouts, and rows with scheduled targets: one column per lane
+        for (uint32_t j0 = 0; j0 < d.NP; j0 += WAVE) {
+            const uint32_t j = j0 + (uint32_t)lane;
+            bool stale = false;
+            if (j < d.ncol) {
+                const size_t pA = ra + j, pB = rb + j;
+                const bool pa = GENM ? d.pos[pA] != NONE : true, pb = GENM ? d.pos[pB] != NONE : true;
+                const bool sa = schA && pa && is_sched(dead_tod(d, pA), t, d.sched_delay);
+                const bool sb = schB && pb && is_sched(dead_tod(d, pB), t, d.sched_delay);
+                const uint32_t R = d.self_hb[j];
+                const uint32_t hA = pa ? hb_view(d, pA, R) : 0u, hB = (w1 && pb) ? hb_view(d, pB, R) : 0u;
+                const uint32_t mA = pa ? (mv_word(d, pA, j) & MV_MASK) : 0u, mB = pb ? (mv_word(d, pB, j) & MV_MASK) : 0u;
+                const uint32_t gA = (gct && pa) ? d.gc[pA] : 0u, gB = (gct && pb) ? d.gc[pB] : 0u;
+                dig += tc_col(w1, d.col_lo + j == ub, pa, pb, sa, sb, hA, hB, gA, gB, mA, mB, d.nid_size[j], stale);
+            }
+            const unsigned long long m = __ballot(stale);
+            if (lane == 0) { bits[j0 >> 5] = (uint32_t)m; bits[(j0 >> 5) + 1] = (uint32_t)(m >> 32); }
+        }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    const uint32_t snd = w1 ? ua : ub, rcv = w1 ? ub : ua;
+    const uint32_t cntS = GENM ? d.row[snd * 4 + 0] : d.ncol, cntR = GENM ? d.row[rcv * 4 + 0] : d.ncol;
+    const DigestSide ds{rcv, cntR, w1 ? schB : schA};
+    WStats st{0, 0, 0, 0, 0};
+    bool tomb = false;
+    PackState pst{0u, false, false};
+    pack_dir<KW, GENM, false, true>(d, snd, rcv, ds, GENM ? d.ord + (size_t)snd * d.NP : nullptr, cntS, bits, wbuf, t, st,
+                                    tomb, pst, nullptr, nullptr);
+    const uint32_t digs = (uint32_t)wave_sum(dig);
+    if (lane == 0) {
+        s_sz[w] = digs;
+        s_sz[2 + w] = pst.S;
+    }
+    __syncthreads();
+    if (threadIdx.x != 0) return;
+    const uint32_t m0 = s_sz[0], m1 = s_sz[1], m2 = s_sz[2], m3 = s_sz[3];
+    if (a.msg) {
+        a.msg[(size_t)e * 4 + 0] = m0;
+        a.msg[(size_t)e * 4 + 1] = m1;
+        a.msg[(size_t)e * 4 + 2] = m2;
+        a.msg[(size_t)e * 4 + 3] = m3;
+    }
+    // PacketPb {cluster_id = 1, syn = 2 {digest = 2} | synack = 3 {digest = 2, delta = 3} | ack = 4 {delta = 3}}
+    const uint32_t head = sfield(a.cid);
+    const uint32_t pk[3] = {head + msgf(msgf(m0)), head + msgf(msgf(m1) + msgf(m2)), head + msgf(msgf(m3))};
+    const bool limit = a.flags & GS_TC_FRAME_LIMIT;
+    bool sent[3], dlv[3];
+    bool go = true;
+    uint32_t lo = 0;
+#pragma unroll
+    for (uint32_t k = 0; k < 3u; k++) {
+        sent[k] = go;
+        dlv[k] = go && lg > k && !(limit && pk[k] > d.mtu);
+        go = dlv[k];
+        lo += dlv[k] ? 1u : 0u;
+    }
+    if (a.legs_out) a.legs_out[e] = (uint8_t)lo;
+    const uint32_t fr[3] = {pk[0] + 4u, pk[1] + 4u, pk[2] + 4u};  // add_msg_size (server.py:516-521)
+    if (a.nodes) {
+        const unsigned long long sa_ = fr[0] + (sent[2] ? fr[2] : 0u), sb_ = sent[1] ? fr[1] : 0u;
+        const unsigned long long ra_ = dlv[1] ? fr[1] : 0u, rb_ = (dlv[0] ? fr[0] : 0u) + (dlv[2] ? fr[2] : 0u);
+        atomicAdd(&a.nodes[ua], sa_);
+        if (sb_) atomicAdd(&a.nodes[ub], sb_);
+        if (ra_) atomicAdd(&a.nodes[d.N + ua], ra_);
+        if (rb_) atomicAdd(&a.nodes[d.N + ub], rb_);
+    }
+    if (a.acc) {
+        unsigned long long *acc = a.acc + (size_t)(e % NSHARD) * TC_NUM;
+        atomicAdd(&acc[TC_EXCH], 1ull);
+#pragma unroll
+        for (uint32_t k = 0; k < 3u; k++) {
+            if (!sent[k]) continue;
+            atomicAdd(&acc[TC_SENT + k], 1ull);
+            atomicAdd(&acc[TC_BSENT + k], (unsigned long long)fr[k]);
+            atomicMax(&acc[TC_MAXF + k], (unsigned long long)fr[k]);
+            atomicAdd(&acc[TC_HIST + k * GS_TC_BUCKETS + tc_bucket(fr[k])], 1ull);
+            if (dlv[k]) {
+                atomicAdd(&acc[TC_DELIV + k], 1ull);
+                atomicAdd(&acc[TC_BDELIV + k], (unsigned long long)fr[k]);
+            } else if (lg <= k) {
+                atomicAdd(&acc[TC_LOST + k], 1ull);
+            } else {
+                atomicAdd(&acc[TC_REJ + k], 1ull);
+            }
+        }
+        atomicAdd(&acc[TC_DIG_SENT], (unsigned long long)m0 + (sent[1] ? m1 : 0u));
+        const unsigned long long ds_ = (sent[1] ? m2 : 0u) + (unsigned long long)(sent[2] ? m3 : 0u);
+        const unsigned long long dd_ = (dlv[1] ? m2 : 0u) + (unsigned long long)(dlv[2] ? m3 : 0u);
+        if (ds_) atomicAdd(&acc[TC_DEL_SENT], ds_);
+        if (dd_) atomicAdd(&acc[TC_DEL_DELIV], dd_);
+    }
+}
+
 // ------------------------------------------------------------------ peer selection
 // select_nodes_for_gossip (server.py:656-717) for every up node from its failure detector's
 // live / dead sets and its known peers, as _gossip_multiple uses them at round start
@@ -6173,6 +6428,7 @@ struct gs_handle {
     unsigned long long *vc_buf = nullptr;  // gs_view_census scratch: VC_NUM u64 accumulators, then the probes
     std::vector<uint64_t> vc_img;          // ... and its host image (the upload before, the read after the pass)
     unsigned long long *dc_buf = nullptr;  // gs_detect_census scratch: DC_NUM u64 accumulators
+    unsigned long long *tc_buf = nullptr;  // gs_traffic_census scratch: NSHARD rows of TC_NUM u64 accumulators
     hipStream_t hside = nullptr;    // k_pack_heavy's stream (forked after the lite slot work, joined after the packer)
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> tev[GS_KT_KINDS];
@@ -6787,6 +7043,7 @@ void gs_destroy(gs_handle *h) {
     if (h->sm_buf) (void)hipFree(h->sm_buf);
     if (h->vc_buf) (void)hipFree(h->vc_buf);
     if (h->dc_buf) (void)hipFree(h->dc_buf);
+    if (h->tc_buf) (void)hipFree(h->tc_buf);
     if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
     if (h->ev_join) (void)hipEventDestroy(h->ev_join);
     if (h->hside) (void)hipStreamDestroy(h->hside);
@@ -8069,6 +8326,76 @@ int gs_detect_census(gs_handle *h, const uint8_t *up, const uint32_t *down_since
         out->up_over[i] = acc[DC_OVER + i];
         out->down_over[i] = acc[DC_OVER + GS_DC_MAX_THRESHOLDS + i];
     }
+    return GS_OK;
+}
+
+static_assert(sizeof(gs_traffic_totals) == TC_NUM * 8, "gs_traffic_totals layout");
+
+extern "C++" {
+namespace {
+template <int KW, bool GENM>
+int launch_traffic(gs_handle *h, const TcArgs &a, size_t lds) {
+    auto *k = k_traffic<KW, GENM>;
+    if (lds > 64 * 1024)
+        HIPCHK(h, hipFuncSetAttribute((const void *)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    k<<<a.n, XB, lds, h->stream>>>(h->d, a);
+    HIPCHK(h, hipGetLastError());
+    return GS_OK;
+}
+}  // namespace
+}  // extern "C++"
+
+int gs_traffic_census(gs_handle *h, const int32_t *ini, const int32_t *res, const uint8_t *legs, uint32_t n, uint32_t tick,
+                      uint32_t cluster_id_len, uint32_t flags, uint32_t *msg, uint8_t *legs_out, uint64_t *nodes,
+                      gs_traffic_totals *out) {
+    if (!h) return GS_E_INVALID;
+    if (n && (!ini || !res)) return fail(h, GS_E_INVALID, "gs_traffic_census: initiators or responders is NULL");
+    if (flags & ~GS_TC_FRAME_LIMIT) return fail(h, GS_E_INVALID, "gs_traffic_census: unknown flag bits 0x%x", flags);
+    if (!msg && !legs_out && !nodes && !out) return fail(h, GS_E_INVALID, "gs_traffic_census: every output is NULL");
+    if ((int32_t)(tick - h->max_tick) < 0 || tick - h->max_tick >= FD_OLD_AGE)
+        return fail(h, GS_E_INVALID, "gs_traffic_census: tick %u is before the handle's latest tick %u, or 2^15 or more "
+                    "past it", tick, h->max_tick);
+    if (!h->booted) return fail(h, GS_E_INVALID, "gs_traffic_census: not booted");
+    if (h->sliced || h->G > 1 || h->comm)
+        return fail(h, GS_E_UNSUPPORTED, "gs_traffic_census: one-slice handles only (the mtu walk crosses slices)");
+    hipStream_t s = h->stream;
+    if (out) {
+        if (!h->tc_buf) HIPCHK(h, hipMalloc(&h->tc_buf, (size_t)NSHARD * TC_NUM * 8));
+        HIPCHK(h, hipMemsetAsync(h->tc_buf, 0, (size_t)NSHARD * TC_NUM * 8, s));
+    }
+    if (n) {
+        TcArgs a;
+        a.ini = ini;
+        a.res = res;
+        a.legs = legs;
+        a.n = n;
+        a.t = tick;
+        a.cid = cluster_id_len;
+        a.flags = flags;
+        a.msg = msg;
+        a.legs_out = legs_out;
+        a.nodes = reinterpret_cast<unsigned long long *>(nodes);
+        a.acc = out ? h->tc_buf : nullptr;
+        // per wave: the packer's window list (WIN u16) and the direction's stale-owner bitmap (NP / 32 words)
+        const size_t lds = 2 * ((size_t)WIN * 2 + (size_t)(h->NP / 32) * 4);
+        const bool genm = !(h->cfg.flags & GS_CANONICAL);
+        int rc;
+        if (h->KP <= 16) rc = genm ? launch_traffic<4, true>(h, a, lds) : launch_traffic<4, false>(h, a, lds);
+        else rc = genm ? launch_traffic<KWB, true>(h, a, lds) : launch_traffic<KWB, false>(h, a, lds);
+        if (rc) return rc;
+    }
+    if (!out) return GS_OK;
+    std::vector<uint64_t> acc((size_t)NSHARD * TC_NUM);
+    HIPCHK(h, hipMemcpyAsync(acc.data(), h->tc_buf, acc.size() * 8, hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipStreamSynchronize(s));
+    uint64_t *w = reinterpret_cast<uint64_t *>(out);  // the accumulators are the struct's words, sharded
+    memset(out, 0, sizeof *out);
+    for (int sh = 0; sh < NSHARD; sh++)
+        for (int c = 0; c < TC_NUM; c++) {
+            const uint64_t v = acc[(size_t)sh * TC_NUM + c];
+            if (c >= TC_MAXF && c < TC_MAXF + 3) w[c] = std::max(w[c], v);  // maxima, not sums
+            else w[c] += v;
+        }
     return GS_OK;
 }
 

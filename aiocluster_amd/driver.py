@@ -11,6 +11,14 @@ With ``WorkloadSpec.loss > 0`` every phase carries a device ``legs`` tensor (``r
 ``rd["phases"]``: the messages delivered of each exchange, ``aiocluster_amd.cuts``) and runs through
 ``gs_run_phase_cut``; with peer-selected rounds the legs are drawn on the device (``gs_draw_cuts``).  With
 ``loss == 0`` nothing changes.
+
+With ``WorkloadSpec.frame_limit`` every phase is first sized by ``gs_traffic_census`` with the reference's frame limit
+(after the loss draw, whose legs it takes as what the network delivers), asynchronously, and runs with the census's
+``legs_out``: an exchange stops where the peer would refuse an oversize packet.  A round record may carry
+``rd["traffic_nodes"]`` (device int64 [2, N]: frame bytes sent / accepted per node, added to) and
+``rd["traffic_totals"] = True``, which reads each phase's totals back (one host wait per phase) and accumulates
+them in ``rd["traffic"]``; either of the two also sizes the phases of a round without ``frame_limit`` (nothing is
+refused then: the phase runs with the network's legs).  Without any of the three nothing changes.
 """
 
 from __future__ import annotations
@@ -78,6 +86,8 @@ def prepare(spec, rounds: int, torch, dev) -> list[dict]:
             out[-1]["legs"] = [torch.from_numpy(draw_cuts_q32(a, b, spec.cut_seed, r, i, q32)).to(dev)
                                for i, (a, b) in enumerate(p.phases)]
             out[-1]["loss_q32"], out[-1]["cut_seed"] = q32, spec.cut_seed
+        if getattr(spec, "frame_limit", False):
+            out[-1]["frame_limit"] = True
     return out
 
 
@@ -96,8 +106,14 @@ def run_phases(sims, rd, events=None, group=None, phases=None, legs=None):
     s0 = sims[0]
     if phases is None and legs is None:
         legs = rd.get("legs")
-    if legs is not None and group is not None:
-        raise ValueError("cut exchanges (loss > 0) run on one-slice handles only")
+    limit = bool(rd.get("frame_limit"))
+    framed = limit or bool(rd.get("traffic_totals")) or rd.get("traffic_nodes") is not None
+    if (legs is not None or framed) and group is not None:
+        raise ValueError("cut exchanges (loss > 0, frame_limit) run on one-slice handles only")
+    if framed:
+        from .sim import add_traffic_totals
+
+        rd["traffic"] = None
     for i, (a, b, n, t) in enumerate(rd["phases"] if phases is None else phases):
         if not n:
             continue
@@ -110,7 +126,14 @@ def run_phases(sims, rd, events=None, group=None, phases=None, legs=None):
             e0 = s0.torch.cuda.Event(enable_timing=True)
             e1 = s0.torch.cuda.Event(enable_timing=True)
             e0.record(s0.stream)
-        if legs is not None:
+        if framed:  # size the phase first; it then runs with what the peers would accept
+            tc = s0.traffic_census(t, (a, b), legs=None if legs is None else legs[i], frame_limit=limit,
+                                   nodes=rd.get("traffic_nodes"), totals=bool(rd.get("traffic_totals")))
+            if rd.get("traffic_totals"):
+                rd["traffic"] = add_traffic_totals(rd["traffic"], tc)
+            s0._chk(s0.L.gs_run_phase_cut(s0.h, C.c_void_p(a.data_ptr()), C.c_void_p(b.data_ptr()),
+                                          C.c_void_p(tc["legs_out"].data_ptr()), n, t), "gs_run_phase_cut")
+        elif legs is not None:
             s0._chk(s0.L.gs_run_phase_cut(s0.h, C.c_void_p(a.data_ptr()), C.c_void_p(b.data_ptr()),
                                           C.c_void_p(legs[i].data_ptr()), n, t), "gs_run_phase_cut")
         elif group is None:

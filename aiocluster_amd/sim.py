@@ -142,6 +142,39 @@ def make_config(n: int, k: int, cfg: dict, flags: int, hist_cap: int, shards: in
     return c
 
 
+def traffic_totals_dict(tot) -> dict:
+    """A ``GsTrafficTotals`` as a dict: per-kind fields as lists [syn, synack, ack], ``frame_hist`` as three lists of
+    GS_TC_BUCKETS counts, and ``digest_share`` = DigestPb bytes / all body bytes sent (0.0 when nothing was sent)."""
+    out = {k: int(getattr(tot, k)) for k in _lib.TRAFFIC_SCALAR_FIELDS + _lib.TRAFFIC_BYTE_FIELDS}
+    for k in _lib.TRAFFIC_KIND_FIELDS + ["max_frame"]:
+        out[k] = [int(x) for x in getattr(tot, k)]
+    out["frame_hist"] = [[int(x) for x in row] for row in tot.frame_hist]
+    body = out["digest_bytes_sent"] + out["delta_bytes_sent"]
+    out["digest_share"] = out["digest_bytes_sent"] / body if body else 0.0
+    return out
+
+
+def add_traffic_totals(acc: dict | None, t: dict) -> dict:
+    """Accumulate one census's totals into ``acc`` (a round's phases): sums, except ``max_frame`` (maxima)."""
+    if acc is None:
+        return {k: ([list(r) for r in v] if k == "frame_hist" else list(v) if isinstance(v, list) else v)
+                for k, v in t.items() if k != "legs_out" and k != "msg"}
+    for k, v in t.items():
+        if k in ("legs_out", "msg", "digest_share"):
+            continue
+        if k == "frame_hist":
+            acc[k] = [[x + y for x, y in zip(r0, r1)] for r0, r1 in zip(acc[k], v)]
+        elif k == "max_frame":
+            acc[k] = [max(x, y) for x, y in zip(acc[k], v)]
+        elif isinstance(v, list):
+            acc[k] = [x + y for x, y in zip(acc[k], v)]
+        else:
+            acc[k] += v
+    body = acc["digest_bytes_sent"] + acc["delta_bytes_sent"]
+    acc["digest_share"] = acc["digest_bytes_sent"] / body if body else 0.0
+    return acc
+
+
 def split_owner_batches(ops: list[tuple]) -> list[list[tuple]]:
     """Split owner writes ``(tick, owner, ...)`` into device batches of distinct owners.
 
@@ -667,6 +700,52 @@ class GossipSim:
              out["target_last_tod"]) = targets[0], targets[1], targets[2], targets[3]
         if per_row:
             out["row_false_suspicions"], out["row_undetected"] = rows[0], rows[1]
+        return out
+
+    def traffic_census(self, t: int, pairs, legs=None, frame_limit: bool = False, cluster_id: str = "default-cluster",
+                       per_exchange: bool = False, nodes=None, totals: bool = True) -> dict:
+        """gs_traffic_census: what the phase ``run_phase(t, pairs, legs)`` would put on the wire, on the state as
+        it stands (a read-only dry run; nothing changes).  ``pairs``: [n, 2] (or a pair of device int32 tensors);
+        ``legs``: what the network delivers per exchange (default 3).  With ``frame_limit`` a delivered message whose
+        packet exceeds the mtu is refused, as the reference's ``_read_message`` does (``server.py:502-514``).
+        Always returns ``legs_out`` (device uint8 [n]: the messages delivered and accepted, the legs to run the
+        phase with).  ``per_exchange`` adds ``msg`` (device int32 [n, 4]: Syn digest, SynAck digest, SynAck delta,
+        Ack delta bytes); ``nodes`` (device int64 [2, N], ADDED to: frame bytes sent / accepted per node) is passed
+        through; ``totals`` (blocking) adds the fields of ``gs_traffic_totals`` -- per-kind lists are ordered
+        syn, synack, ack -- and ``digest_share`` of all body bytes sent.  With ``totals=False`` the call is
+        asynchronous on the sim's stream."""
+        self._flush()
+        if "gs_traffic_census" in self.L.gs_missing:
+            raise GsError("gs_traffic_census: this GS_LIB build lacks the entry point")
+        torch = self.torch
+        if isinstance(pairs, tuple) and hasattr(pairs[0], "data_ptr"):
+            ini, res = pairs
+        else:
+            arr = np.asarray(pairs, dtype=np.int32).reshape(-1, 2)
+            ini, res = self._pairs_dev(arr[:, 0], arr[:, 1])
+        n = int(ini.numel())
+        lg = None
+        if legs is not None:
+            lg = legs if hasattr(legs, "data_ptr") else self._dev(np.asarray(legs, np.uint8), torch.uint8)
+            if lg.dtype != torch.uint8 or int(lg.numel()) != n:
+                raise GsError(f"legs: one uint8 per exchange (got {int(lg.numel())} {lg.dtype} for {n} exchanges)")
+        if nodes is not None and (nodes.dtype != torch.int64 or tuple(nodes.shape) != (2, self.n)):
+            raise GsError(f"nodes: a device int64 tensor [2, {self.n}]")
+        legs_out = torch.empty(n, dtype=torch.uint8, device=self.device)
+        msg = torch.empty((n, 4), dtype=torch.int32, device=self.device) if per_exchange else None
+        tot = _lib.GsTrafficTotals() if totals else None
+
+        def ptr(x):
+            return C.c_void_p(x.data_ptr()) if x is not None else None
+
+        self._chk(self.L.gs_traffic_census(self.h, ptr(ini), ptr(res), ptr(lg), n, int(t), len(cluster_id.encode()),
+                                           _lib.GS_TC_FRAME_LIMIT if frame_limit else 0, ptr(msg), ptr(legs_out),
+                                           ptr(nodes), C.byref(tot) if totals else None), "gs_traffic_census")
+        out = {"legs_out": legs_out}
+        if per_exchange:
+            out["msg"] = msg
+        if totals:
+            out.update(traffic_totals_dict(tot))
         return out
 
     def reach(self, owner: int, version: int | None = None, up=None) -> int:

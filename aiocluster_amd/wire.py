@@ -22,6 +22,7 @@ import numpy as np
 
 from . import _lib
 from .entities import NodeId
+from .pbsize import msg_field, s_field
 
 
 def varint(x: int) -> bytes:
@@ -71,6 +72,24 @@ def packet(cluster_id: str, kind: str, digest: bytes | None = None, delta: bytes
 def frame(pkt: bytes) -> bytes:
     """``add_msg_size``: the 4-byte big-endian size prefix of a TCP frame (``server.py:516-521``)."""
     return len(pkt).to_bytes(4, "big") + pkt
+
+
+def packet_size(kind: str, digest_len: int = 0, delta_len: int = 0, cluster_id: str = "default-cluster") -> int:
+    """``len(packet(cluster_id, kind, digest, delta))`` from the body lengths alone: the closed form
+    ``gs_traffic_census`` uses (``include/gossip_sim.h``)."""
+    head = s_field(len(cluster_id.encode()))
+    if kind == "syn":
+        return head + msg_field(msg_field(digest_len))
+    if kind == "synack":
+        return head + msg_field(msg_field(digest_len) + msg_field(delta_len))
+    if kind == "ack":
+        return head + msg_field(msg_field(delta_len))
+    raise ValueError(kind)
+
+
+def frame_size(kind: str, digest_len: int = 0, delta_len: int = 0, cluster_id: str = "default-cluster") -> int:
+    """``len(frame(packet(...)))``: the packet and its 4-byte size prefix, the bytes on the wire."""
+    return 4 + packet_size(kind, digest_len, delta_len, cluster_id)
 
 
 class WireEmitter:

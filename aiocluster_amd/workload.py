@@ -148,6 +148,9 @@ class WorkloadSpec:
     # probability, drawn from cut_seed; the schedule itself does not change (driver.prepare adds the legs)
     loss: float = 0.0
     cut_seed: int = 0
+    # the reference's frame limit (server.py:502-514): before every phase gs_traffic_census sizes its messages, and an
+    # exchange stops where the peer would refuse an oversize packet (the phase runs with the census's legs_out)
+    frame_limit: bool = False
     extra: dict = field(default_factory=dict)
 
 

@@ -564,6 +564,58 @@ int gs_detect_census(gs_handle *h, const uint8_t *up /*DEVICE [N]*/, const uint3
                      uint32_t *targets /*DEVICE [4][ncol] or NULL*/, uint32_t *rows /*DEVICE [2][N] or NULL*/,
                      gs_detect_totals *out /*HOST*/);
 
+/* Traffic census: what a phase costs on the wire, and which of its frames the peer would refuse.  A read-only dry
+ * run of the phase gs_run_phase_cut(h, initiators, responders, ., n, tick) would run, on the state as it stands: one
+ * pass over both rows of every exchange, no region and no field of gs_read_counters changes.  The pairs need not be
+ * conflict-free and n is not bound by N/2 (no per-phase scratch region is used).
+ *   msg[e] (DEVICE u32 [n][4] or NULL): four body sizes in bytes of exchange e = (a -> b), computed whether or not the
+ *     message is reached: {0: the DigestPb of a's compute_digest at `tick` (gs_emit_digest's size); 1: b's DigestPb as
+ *     _handle_syn_msg builds it (server.py:334-340) -- after b's own inc_heartbeat and _report_heartbeat over a's
+ *     digest: b's own entry carries its heartbeat + 1, an owner j != b of a's digest max(b's view, a's view), an owner b
+ *     did not know enters with a's heartbeat, last_gc 0 and max_version 0, b's scheduled targets are left out; 2: the
+ *     DeltaPb of b's compute_partial_delta_respecting_mtu against a's digest (gs_emit_delta(b, a)'s size); 3: a's
+ *     DeltaPb against b's digest on a's pre-exchange views (gs_emit_delta(a, b)'s size: the two deltas commute)}.
+ *   Packets (PacketPb, server.py:327-370), C = cluster_id_len, sf / mf = a string / an embedded message field
+ *     (aiocluster_amd/pbsize.py): Syn sf(C) + mf(mf(msg[0])), SynAck sf(C) + mf(mf(msg[1]) + mf(msg[2])), Ack
+ *     sf(C) + mf(mf(msg[3])).  A frame -- the bytes on the wire -- is the packet + 4 (add_msg_size, server.py:516-521).
+ *   legs (DEVICE u8 [n] or NULL = 3): what the network delivers, as for gs_run_phase_cut.  The Syn is always sent; the
+ *     SynAck iff the Syn was delivered and accepted; the Ack iff the SynAck was.  With GS_TC_FRAME_LIMIT a delivered
+ *     message whose packet exceeds gs_config.mtu is rejected (_read_message, server.py:502-514: sent, not delivered),
+ *     which leaves the state of a cut exchange.  legs_out[e] (DEVICE u8 [n] or NULL) = the messages delivered and
+ *     accepted, the value to hand to gs_run_phase_cut; without the flag legs_out = legs.
+ *   nodes (DEVICE u64 [2][N] or NULL): ADDED to, not overwritten (the caller clears it; one buffer collects a round's
+ *     phases): nodes[0][i] = frame bytes node i sent, nodes[1][i] = frame bytes it accepted.
+ *   out (HOST or NULL): the totals, overwritten.  out == NULL: nothing is read back and the call is asynchronous on the
+ *     handle's stream; otherwise it blocks.
+ * An exchange with an endpoint out of range, a == b or legs > 3 gets four zeros and legs_out 0, and is counted in
+ * bad_index and nowhere else.
+ * GS_E_INVALID (checked before any device work): h NULL; initiators or responders NULL with n > 0; unknown flag bits;
+ * all four outputs NULL; tick below gs_latest_tick, or 2^15 or more past it.  GS_E_UNSUPPORTED: sliced handles
+ * (n_shards > 1, GS_SLICED, or a communicator): the mtu walk crosses slices, as for gs_emit_delta / gs_run_phase_cut. */
+#define GS_TC_FRAME_LIMIT 1u   /* apply _read_message's limit (packet bytes > gs_config.mtu) */
+#define GS_TC_BUCKETS 32u      /* bucket 0: 0 bytes; bucket b >= 1: 2^(b-1) <= frame bytes < 2^b */
+typedef struct gs_traffic_totals {   /* all u64, 128 words; [3] = by message kind: 0 Syn, 1 SynAck, 2 Ack */
+    uint64_t exchanges;              /* valid exchanges */
+    uint64_t bad_index;              /* invalid exchanges (counted nowhere else) */
+    uint64_t sent[3];                /* messages sent */
+    uint64_t delivered[3];           /* ... delivered and accepted */
+    uint64_t lost[3];                /* ... sent and lost to the network (legs) */
+    uint64_t rejected[3];            /* ... sent, delivered and refused as oversize (GS_TC_FRAME_LIMIT) */
+    uint64_t bytes_sent[3];          /* frame bytes of the messages sent */
+    uint64_t bytes_delivered[3];     /* frame bytes of the messages delivered and accepted */
+    uint64_t digest_bytes_sent;      /* DigestPb bodies of the Syns and SynAcks sent */
+    uint64_t delta_bytes_sent;       /* DeltaPb bodies of the SynAcks and Acks sent */
+    uint64_t delta_bytes_delivered;  /* ... delivered and accepted: what gs_run_phase_cut with legs_out adds to gs_counters.delta_bytes */
+    uint64_t max_frame[3];           /* largest frame sent */
+    uint64_t frame_hist[3][GS_TC_BUCKETS];   /* over the messages sent */
+    uint64_t reserved[6];
+} gs_traffic_totals;
+int gs_traffic_census(gs_handle *h, const int32_t *initiators, const int32_t *responders,
+                      const uint8_t *legs /*DEVICE u8[n] or NULL = 3*/, uint32_t n, uint32_t tick,
+                      uint32_t cluster_id_len, uint32_t flags,
+                      uint32_t *msg /*DEVICE [n][4] or NULL*/, uint8_t *legs_out /*DEVICE [n] or NULL*/,
+                      uint64_t *nodes /*DEVICE [2][N] or NULL*/, gs_traffic_totals *out /*HOST or NULL*/);
+
 /* Wire-format emitter: the protobuf bytes the reference's SerializeToString gives, from device state,
  * so a simulated cluster can talk to real aiocluster nodes (messages.proto:46-74).  String tables are
  * DEVICE arrays owned by the caller: NodeIdPb bytes of every node (entities.py:62-72; node i at

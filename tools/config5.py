@@ -42,6 +42,9 @@ def main():
     ap.add_argument("--loss", type=float, default=0.0,
                     help="probability that a Syn / SynAck / Ack is lost (gs_run_phase_cut): the false-positive rate "
                          "under message loss")
+    ap.add_argument("--frame-limit", action="store_true",
+                    help="refuse frames larger than the mtu, as the reference's _read_message does (gs_traffic_census "
+                         "before every phase)")
     args = ap.parse_args()
 
     import torch
@@ -59,7 +62,7 @@ def main():
     cfg["tombstone_grace_s"] = 10
     spec = WorkloadSpec(n=n, k=K, fanout=args.fanout, seed=args.seed, init="warm", write_frac=0.05,
                         delete_frac=0.01, partition=(args.warm, args.warm + args.partition), loss=args.loss,
-                        cut_seed=args.seed)
+                        cut_seed=args.seed, frame_limit=args.frame_limit)
     boot = boot_ops(n, K)
     t0 = time.perf_counter()
     sim = GossipSim(synthetic_node_ids(n), key_names(K), cfg, init="warm", device=str(dev), tombstones=True,
@@ -100,6 +103,7 @@ def main():
     out = {
         "config": "BASELINE config 5",
         "loss": args.loss,
+        "frame_limit": args.frame_limit,
         "workload": f"N={n} K={K} F={args.fanout} warm, 5% writes (1% deletes), tombstone grace 10 rounds, "
                     f"mtu 65507, partition into halves for rounds [{args.warm}, {args.warm + args.partition}) "
                     f"then heal for {args.heal} rounds",

@@ -54,6 +54,9 @@ def main():
     ap.add_argument("--wide-views", action="store_true", help="16-bit views instead of GS_HB8 + GS_MV8")
     ap.add_argument("--loss", type=float, default=0.0,
                     help="probability that a Syn / SynAck / Ack is lost (gs_run_phase_cut): the curve under loss")
+    ap.add_argument("--frame-limit", action="store_true",
+                    help="refuse frames larger than the mtu, as the reference's _read_message does (gs_traffic_census "
+                         "before every phase): the curve of a real deployment")
     args = ap.parse_args()
 
     import numpy as np
@@ -69,7 +72,8 @@ def main():
     torch.cuda.set_device(dev)
     cfg = dict(DEFAULT_CFG)
     spec = WorkloadSpec(n=n, k=K, fanout=args.fanout, seed=args.seed, init="warm", write_frac=0.05, down_frac=0.05,
-                        down_rounds=3, quiet_from=args.settle, loss=args.loss, cut_seed=args.seed)
+                        down_rounds=3, quiet_from=args.settle, loss=args.loss, cut_seed=args.seed,
+                        frame_limit=args.frame_limit)
     sim = GossipSim(synthetic_node_ids(n), key_names(K), cfg, init="warm", device=str(dev), tombstones=False,
                     fd_ring=False, hist_cap=64, initial_ops=driver.boot_ops(n, K), hb8=not args.wide_views,
                     mv8=not args.wide_views)
@@ -172,6 +176,7 @@ def main():
                     f"rounds of 5% writes + 5% down churn, then {len(probes)} fresh writes and {args.rounds} quiet rounds"
                     + (f"; message loss {args.loss}" if args.loss else ""),
         "loss": args.loss,
+        "frame_limit": args.frame_limit,
         "cut_exchanges": sim.counters()["cut_exchanges"],
         "probes": [{"owner": j, "version": v, "rounds_to_50pct": rounds_to(0.5, i), "rounds_to_99pct": rounds_to(0.99, i),
                     "rounds_to_100pct": rounds_to(1.0, i)} for i, (j, v) in enumerate(probes)],
