@@ -29,6 +29,10 @@ GS_MV8 = 32  # 8-bit max_version views
 GS_SLICED = 64  # the sliced phase path with one slice (a world-1 run of the multi-GPU code)
 GS_NONE = 0xFFFFFFFF
 GS_E_INVALID = -1
+GS_E_UNSUPPORTED = -5
+GS_MAX_ZONES = 16  # zoned links (gs_draw_cuts_zoned, gs_filter_targets_zoned)
+GS_LINK_DOWN = 0xFFFFFFFF  # a link that carries nothing
+GS_LEGS_NO_CONNECT = 255  # legs of a pair whose connect would fail
 GS_MV_INEXACT = 0x8000
 TICK_US = 15_625
 
@@ -93,7 +97,7 @@ EXPORTS = [
     "gs_check_heartbeat_lag", "gs_stream_copy", "gs_stream_read", "gs_stream_write", "gs_set_timing", "gs_kernel_times",
     "gs_phase_overflow", "gs_phase_chain", "gs_phase_pending", "gs_comm_id", "gs_comm_init", "gs_run_phase_group", "gs_read_rows",
     "gs_latest_tick", "gs_flush_reports", "gs_set_ring_rows", "gs_mark", "gs_view_census", "gs_run_phase_cut", "gs_draw_cuts",
-    "gs_detect_census", "gs_traffic_census",
+    "gs_detect_census", "gs_traffic_census", "gs_draw_cuts_zoned", "gs_filter_targets_zoned", "gs_detect_census_for",
 ]
 
 API_VERSION = 23
@@ -268,6 +272,8 @@ def load():
         "gs_run_phase": (C.c_int, [P, P, P, u32, u32]),
         "gs_run_phase_cut": (C.c_int, [P, P, P, P, u32, u32]),
         "gs_draw_cuts": (C.c_int, [P, P, P, u32, u64, u32, u32, u32, P]),
+        "gs_draw_cuts_zoned": (C.c_int, [P, P, P, u32, u64, u32, u32, P, C.POINTER(u32), u32, P]),
+        "gs_filter_targets_zoned": (C.c_int, [P, P, P, u32, P, C.POINTER(u32), u32, P]),
         "gs_liveness": (C.c_int, [P, P, u32]),
         "gs_phi_row": (C.c_int, [P, u32, u32, P]),
         "gs_read_counters": (C.c_int, [P, C.POINTER(GsCounters)]),
@@ -292,6 +298,8 @@ def load():
         "gs_fd_census": (C.c_int, [P, P, C.POINTER(GsCensus)]),
         "gs_view_census": (C.c_int, [P, P, u32, C.POINTER(GsProbe), u32, C.POINTER(u64), P, P, C.POINTER(GsViewTotals)]),
         "gs_detect_census": (C.c_int, [P, P, P, u32, C.POINTER(C.c_double), u32, P, P, C.POINTER(GsDetectTotals)]),
+        "gs_detect_census_for": (C.c_int, [P, P, P, P, u32, C.POINTER(C.c_double), u32, P, P,
+                                           C.POINTER(GsDetectTotals)]),
         "gs_traffic_census": (C.c_int, [P, P, P, P, u32, u32, u32, u32, P, P, P, C.POINTER(GsTrafficTotals)]),
         "gs_set_events": (C.c_int, [P, P, u32, P]),
         "gs_select_peers": (C.c_int, [P, P, u32, P, u32, C.c_uint64, u32, P, P]),

@@ -4782,7 +4782,9 @@ __global__ __launch_bounds__(LB, 4) void k_view_census(Dev d, VcArgs a, uint32_t
 // the undetected failures and of the false suspicions, and the pairs whose phi exceeds each swept threshold.
 // k_view_census's access pattern: one workgroup per (band of DC_BAND observer rows, chunk of LB x 16 columns), one
 // 16-byte non-temporal load of the state bytes per thread and row, rows in flight ahead of the one being reduced;
-// rows of down observers are neither loaded nor reduced (a wave-uniform choice).  The chunk's up bytes become two
+// rows that are not counted are neither loaded nor reduced (a wave-uniform choice).  The rows counted are those of
+// DcArgs.obs, the targets' truth is DcArgs.up: gs_detect_census passes one array for both, gs_detect_census_for two
+// (an observer set that is one side of a partition, against what that side can reach).  The chunk's up bytes become two
 // byte masks per word (held in registers), down_since lives in LDS.
 // State only: four pairs per 32-bit word -- live and dead bytes by two bit operations, masked by the targets'
 // validity, accumulated in byte counters (widened every 128 rows).  The totals and the undetected ages follow from
@@ -4800,7 +4802,8 @@ enum DcSlot {
     DC_OVER = DC_HIST + 3 * GS_DC_BUCKETS, DC_NUM = DC_OVER + 2 * GS_DC_MAX_THRESHOLDS
 };
 struct DcArgs {
-    const uint8_t *up;
+    const uint8_t *obs;          // the rows counted (gs_detect_census: obs == up)
+    const uint8_t *up;           // the targets' truth
     const uint32_t *down_since;  // nullptr: no latency / undetected-age histograms
     uint32_t tick, tdec;         // tdec = the handle's latest tick: GS_R_FD_LAST decodes exactly against it
     uint32_t n_thr;
@@ -4835,7 +4838,7 @@ __global__ __launch_bounds__(LB, PHI ? 2 : 4) void k_detect_census(Dev d, DcArgs
     s_rows[tid] = 0u;
     // rows of down observers are neither loaded nor reduced: every load of the loop below is unconditional, so the
     // compiler's wait for a row leaves the later rows in flight
-    const bool cnt_row = tid < nrow && a.up[o0 + tid];
+    const bool cnt_row = tid < nrow && a.obs[o0 + tid];
     const unsigned long long cnt_b = __ballot(cnt_row);
     if ((tid & 63u) == 0u) s_wc[tid >> 6] = (uint32_t)__popcll(cnt_b);
     // the targets' truth: byte masks of the up and the down columns, four columns per word
@@ -4900,7 +4903,7 @@ __global__ __launch_bounds__(LB, PHI ? 2 : 4) void k_detect_census(Dev d, DcArgs
 #pragma unroll
     for (uint32_t k = 0; k < 16u; k++) { tmin[k] = NONE; tmax[k] = 0u; }
     const uint32_t n_obs = nlist;
-    uint32_t n_diag = 0, t_early = 0, t_maxlat = 0, t_maxfalse = 0;
+    uint32_t n_diag = 0, n_diag_dn = 0, t_early = 0, t_maxlat = 0, t_maxfalse = 0;
     uint32_t t_upwin = 0, t_dnwin = 0, t_upphi = 0, t_dnphi = 0, t_old = 0, t_upall = 0, t_dnall = 0;
     const uint32_t sum_mask = (1u << d.sum_bits) - 1u;
     auto row = [&](uint32_t r, const Row &rw) {
@@ -4914,7 +4917,10 @@ __global__ __launch_bounds__(LB, PHI ? 2 : 4) void k_detect_census(Dev d, DcArgs
                     n_diag++;
 #pragma unroll
                     for (uint32_t q = 0; q < 4u; q++)
-                        if ((dj >> 2) == q) sw[q] &= ~(0xFFu << (8u * (dj & 3u)));
+                        if ((dj >> 2) == q) {  // (obs != up: a counted observer may itself be a down target)
+                            sw[q] &= ~(0xFFu << (8u * (dj & 3u)));
+                            n_diag_dn += (dnm[q] >> (8u * (dj & 3u))) & 1u;
+                        }
                 }
 #pragma unroll
                 for (uint32_t q = 0; q < 4u; q++) {
@@ -5041,7 +5047,7 @@ __global__ __launch_bounds__(LB, PHI ? 2 : 4) void k_detect_census(Dev d, DcArgs
     }
     {
         const uint32_t lane0 = (tid & 63u) == 0u;
-        const uint32_t up_pairs = n_obs * upcnt - n_diag, dn_pairs = n_obs * dncnt;
+        const uint32_t up_pairs = n_obs * upcnt - (n_diag - n_diag_dn), dn_pairs = n_obs * dncnt - n_diag_dn;
         const uint32_t v[12] = {up_pairs, t_ul, t_ud, dn_pairs, t_dl, t_dd, t_upwin, t_dnwin, t_upphi, t_dnphi, t_old, t_early};
 #pragma unroll
         for (uint32_t i = 0; i < 12u; i++) {
@@ -5838,6 +5844,64 @@ __global__ __launch_bounds__(LB) void k_draw_cuts(const int32_t *ini, const int3
     uint32_t c[4] = {round, (uint32_t)ini[e], (uint32_t)res[e], phase};
     philox4x32(c, (uint32_t)seed, (uint32_t)(seed >> 32));
     legs[e] = c[0] < loss_q32 ? 0u : c[1] < loss_q32 ? 1u : c[2] < loss_q32 ? 2u : 3u;
+}
+
+// Zoned links (gs_draw_cuts_zoned, gs_filter_targets_zoned): link[x * Z + y] = the loss threshold of a message from a
+// node of zone x to a node of zone y, GS_LINK_DOWN = the link carries nothing.  The matrix travels as a kernel
+// argument (1 KiB) and is staged in LDS, where every lane looks up its own two entries.
+struct ZoneLinks {
+    uint32_t q[GS_MAX_ZONES * GS_MAX_ZONES];
+};
+static_assert(LB >= (int)(GS_MAX_ZONES * GS_MAX_ZONES), "one thread per link entry stages the matrix");
+// the two thresholds of the pair a -> b (forward: Syn and Ack, backward: SynAck); false = the connect fails: an index
+// or a zone byte out of range, or either direction down (asyncio.wait_for(open_coro), server.py:403-405, 424-431)
+__device__ __forceinline__ bool zone_pair(const uint32_t *s_link, const uint8_t *zone, uint32_t N, uint32_t Z,
+                                          uint32_t a, uint32_t b, uint32_t &fwd, uint32_t &bwd) {
+    if (a >= N || b >= N) return false;
+    const uint32_t za = zone[a], zb = zone[b];
+    if (za >= Z || zb >= Z) return false;
+    fwd = s_link[za * Z + zb];
+    bwd = s_link[zb * Z + za];
+    return fwd != GS_LINK_DOWN && bwd != GS_LINK_DOWN;
+}
+// gs_draw_cuts_zoned: k_draw_cuts with the threshold of each message's direction; a pair whose connect fails gets
+// GS_LEGS_NO_CONNECT.  Restated on the CPU by aiocluster_amd/cuts.py (draw_cuts_zoned).
+__global__ __launch_bounds__(LB) void k_draw_cuts_zoned(const int32_t *ini, const int32_t *res, uint32_t n, uint32_t N,
+                                                        uint64_t seed, uint32_t round, uint32_t phase,
+                                                        const uint8_t *zone, ZoneLinks lk, uint32_t Z, uint8_t *legs) {
+    __shared__ uint32_t s_link[GS_MAX_ZONES * GS_MAX_ZONES];
+    if (threadIdx.x < Z * Z) s_link[threadIdx.x] = lk.q[threadIdx.x];
+    __syncthreads();
+    const uint32_t e = blockIdx.x * LB + threadIdx.x;
+    if (e >= n) return;
+    const uint32_t a = (uint32_t)ini[e], b = (uint32_t)res[e];
+    uint32_t fwd = 0u, bwd = 0u;
+    if (!zone_pair(s_link, zone, N, Z, a, b, fwd, bwd)) {
+        legs[e] = (uint8_t)GS_LEGS_NO_CONNECT;
+        return;
+    }
+    uint32_t c[4] = {round, a, b, phase};
+    philox4x32(c, (uint32_t)seed, (uint32_t)(seed >> 32));
+    legs[e] = c[0] < fwd ? 0u : c[1] < bwd ? 1u : c[2] < fwd ? 2u : 3u;
+}
+// gs_filter_targets_zoned: the selected targets (gs_select_peers: out[o * per + slot], -1 = none) whose connect
+// would fail become -1; in may alias out (a thread reads and writes its own entry only).
+__global__ __launch_bounds__(LB) void k_zone_filter(const int32_t *in, int32_t *out, uint32_t n_targets, uint32_t per,
+                                                    uint32_t N, const uint8_t *zone, ZoneLinks lk, uint32_t Z,
+                                                    uint32_t *dropped) {
+    __shared__ uint32_t s_link[GS_MAX_ZONES * GS_MAX_ZONES];
+    if (threadIdx.x < Z * Z) s_link[threadIdx.x] = lk.q[threadIdx.x];
+    __syncthreads();
+    const uint32_t e = blockIdx.x * LB + threadIdx.x;
+    bool drop = false;
+    if (e < n_targets) {
+        const int32_t t = in[e];
+        uint32_t fwd, bwd;
+        drop = t >= 0 && !zone_pair(s_link, zone, N, Z, e / per, (uint32_t)t, fwd, bwd);
+        out[e] = drop ? -1 : t;
+    }
+    const unsigned long long m = __ballot(drop);
+    if (dropped && (threadIdx.x & 63) == 0 && m) atomicAdd(dropped, (uint32_t)__popcll(m));
 }
 
 // per row: live / dead / known-peer counts (observer up); SCNT[o] = {live, dead, peers, 0}
@@ -7308,6 +7372,51 @@ int gs_draw_cuts(gs_handle *h, const int32_t *ini, const int32_t *res, uint32_t 
     return GS_OK;
 }
 
+extern "C++" {
+namespace {
+// the checks gs_draw_cuts_zoned and gs_filter_targets_zoned share, and the matrix as a kernel argument
+int zone_args(gs_handle *h, const char *fn, const uint8_t *zone, const uint32_t *link, uint32_t Z, ZoneLinks &lk) {
+    if (!zone) return fail(h, GS_E_INVALID, "%s: zone is NULL", fn);
+    if (!link) return fail(h, GS_E_INVALID, "%s: link is NULL", fn);
+    if (Z < 1 || Z > GS_MAX_ZONES) return fail(h, GS_E_INVALID, "%s: %u zones (1..%u)", fn, Z, GS_MAX_ZONES);
+    if (h->sliced || h->G > 1 || h->comm)
+        return fail(h, GS_E_UNSUPPORTED, "%s: zoned links run on one-slice handles only, as cut exchanges do", fn);
+    memset(&lk, 0, sizeof lk);
+    memcpy(lk.q, link, (size_t)Z * Z * 4);
+    return GS_OK;
+}
+}  // namespace
+}
+
+int gs_draw_cuts_zoned(gs_handle *h, const int32_t *ini, const int32_t *res, uint32_t n, uint64_t seed, uint32_t round,
+                       uint32_t phase, const uint8_t *zone, const uint32_t *link, uint32_t Z, uint8_t *legs) {
+    if (!h) return GS_E_INVALID;
+    if (!ini || !res) return fail(h, GS_E_INVALID, "gs_draw_cuts_zoned: initiators or responders is NULL");
+    if (!legs) return fail(h, GS_E_INVALID, "gs_draw_cuts_zoned: legs is NULL");
+    ZoneLinks lk;
+    if (const int rc = zone_args(h, "gs_draw_cuts_zoned", zone, link, Z, lk)) return rc;
+    if (!n) return GS_OK;
+    k_draw_cuts_zoned<<<(n + LB - 1) / LB, LB, 0, h->stream>>>(ini, res, n, h->N, seed, round, phase, zone, lk, Z, legs);
+    HIPCHK(h, hipGetLastError());
+    return GS_OK;
+}
+
+int gs_filter_targets_zoned(gs_handle *h, const int32_t *targets_in, int32_t *targets_out, uint32_t n_targets,
+                            const uint8_t *zone, const uint32_t *link, uint32_t Z, uint32_t *dropped) {
+    if (!h) return GS_E_INVALID;
+    if (!targets_in || !targets_out)
+        return fail(h, GS_E_INVALID, "gs_filter_targets_zoned: targets_in or targets_out is NULL");
+    ZoneLinks lk;
+    if (const int rc = zone_args(h, "gs_filter_targets_zoned", zone, link, Z, lk)) return rc;
+    if (!n_targets || n_targets % h->N)
+        return fail(h, GS_E_INVALID, "gs_filter_targets_zoned: %u targets are not a whole number of slots for each of "
+                    "%u nodes", n_targets, h->N);
+    k_zone_filter<<<(n_targets + LB - 1) / LB, LB, 0, h->stream>>>(targets_in, targets_out, n_targets, n_targets / h->N,
+                                                                  h->N, zone, lk, Z, dropped);
+    HIPCHK(h, hipGetLastError());
+    return GS_OK;
+}
+
 int gs_shard_columns(const gs_handle *h, uint32_t *col_lo, uint32_t *n_cols) {
     if (!h || !col_lo || !n_cols) return GS_E_INVALID;
     *col_lo = h->col_lo;
@@ -8240,29 +8349,34 @@ int gs_view_census(gs_handle *h, const uint8_t *up, uint32_t flags, const gs_pro
 
 static_assert(sizeof(gs_detect_totals) == 120 * 8, "gs_detect_totals layout");
 
-int gs_detect_census(gs_handle *h, const uint8_t *up, const uint32_t *down_since, uint32_t tick, const double *thresholds,
-                     uint32_t n_thresholds, uint32_t *targets, uint32_t *rows, gs_detect_totals *out) {
+extern "C++" {
+namespace {
+// gs_detect_census (obs == up) and gs_detect_census_for: `fn` names the entry point in gs_last_error
+int detect_census(gs_handle *h, const char *fn, const uint8_t *obs, const uint8_t *up, const uint32_t *down_since,
+                  uint32_t tick, const double *thresholds, uint32_t n_thresholds, uint32_t *targets, uint32_t *rows,
+                  gs_detect_totals *out) {
     if (!h) return GS_E_INVALID;
-    if (!up) return fail(h, GS_E_INVALID, "gs_detect_census: up is NULL");
-    if (!out) return fail(h, GS_E_INVALID, "gs_detect_census: out is NULL");
+    if (!obs) return fail(h, GS_E_INVALID, "%s: observers is NULL", fn);
+    if (!up) return fail(h, GS_E_INVALID, "%s: up is NULL", fn);
+    if (!out) return fail(h, GS_E_INVALID, "%s: out is NULL", fn);
     if (n_thresholds > GS_DC_MAX_THRESHOLDS)
-        return fail(h, GS_E_INVALID, "gs_detect_census: %u thresholds (at most %u)", n_thresholds, GS_DC_MAX_THRESHOLDS);
-    if (n_thresholds && !thresholds) return fail(h, GS_E_INVALID, "gs_detect_census: thresholds is NULL");
+        return fail(h, GS_E_INVALID, "%s: %u thresholds (at most %u)", fn, n_thresholds, GS_DC_MAX_THRESHOLDS);
+    if (n_thresholds && !thresholds) return fail(h, GS_E_INVALID, "%s: thresholds is NULL", fn);
     // gs_create's bound on phi_threshold, for every swept threshold: a window silent for >= 2^15 ticks is above it
     const double widest = std::max((double)h->cfg.max_interval_ticks, h->cfg.prior_weighted / 5.0 * 64.0);
     double tmin = 0.0, tmax = 0.0;
     for (uint32_t i = 0; i < n_thresholds; i++) {
         const double x = thresholds[i];
         if (!(x >= 0.0) || !(x * widest < (double)FD_OLD_AGE))
-            return fail(h, GS_E_INVALID, "gs_detect_census: threshold %u = %g is NaN, negative or too large "
-                        "(threshold x max(max_interval, prior) must stay below 2^15 ticks)", i, x);
+            return fail(h, GS_E_INVALID, "%s: threshold %u = %g is NaN, negative or too large "
+                        "(threshold x max(max_interval, prior) must stay below 2^15 ticks)", fn, i, x);
         tmin = i ? std::min(tmin, x) : x;
         tmax = i ? std::max(tmax, x) : x;
     }
     if ((int32_t)(tick - h->max_tick) < 0 || tick - h->max_tick >= FD_OLD_AGE)
-        return fail(h, GS_E_INVALID, "gs_detect_census: tick %u is before the handle's latest tick %u, or 2^15 or more "
-                    "past it", tick, h->max_tick);
-    if (!h->booted) return fail(h, GS_E_INVALID, "gs_detect_census: not booted");
+        return fail(h, GS_E_INVALID, "%s: tick %u is before the handle's latest tick %u, or 2^15 or more "
+                    "past it", fn, tick, h->max_tick);
+    if (!h->booted) return fail(h, GS_E_INVALID, "%s: not booted", fn);
     if (!h->dc_buf) HIPCHK(h, hipMalloc(&h->dc_buf, (size_t)DC_NUM * 8));
     hipStream_t s = h->stream;
     HIPCHK(h, hipMemsetAsync(h->dc_buf, 0, (size_t)DC_NUM * 8, s));
@@ -8272,6 +8386,7 @@ int gs_detect_census(gs_handle *h, const uint8_t *up, const uint32_t *down_since
     }
     if (rows) HIPCHK(h, hipMemsetAsync(rows, 0, (size_t)2 * h->N * 4, s));
     DcArgs a;
+    a.obs = obs;
     a.up = up;
     a.down_since = down_since;
     a.tick = tick;
@@ -8327,6 +8442,21 @@ int gs_detect_census(gs_handle *h, const uint8_t *up, const uint32_t *down_since
         out->down_over[i] = acc[DC_OVER + GS_DC_MAX_THRESHOLDS + i];
     }
     return GS_OK;
+}
+}  // namespace
+}
+
+int gs_detect_census(gs_handle *h, const uint8_t *up, const uint32_t *down_since, uint32_t tick, const double *thresholds,
+                     uint32_t n_thresholds, uint32_t *targets, uint32_t *rows, gs_detect_totals *out) {
+    if (h && !up) return fail(h, GS_E_INVALID, "gs_detect_census: up is NULL");
+    return detect_census(h, "gs_detect_census", up, up, down_since, tick, thresholds, n_thresholds, targets, rows, out);
+}
+
+int gs_detect_census_for(gs_handle *h, const uint8_t *observers, const uint8_t *up, const uint32_t *down_since,
+                         uint32_t tick, const double *thresholds, uint32_t n_thresholds, uint32_t *targets, uint32_t *rows,
+                         gs_detect_totals *out) {
+    return detect_census(h, "gs_detect_census_for", observers, up, down_since, tick, thresholds, n_thresholds, targets,
+                         rows, out);
 }
 
 static_assert(sizeof(gs_traffic_totals) == TC_NUM * 8, "gs_traffic_totals layout");

@@ -59,6 +59,69 @@ def draw_cuts_q32(ini, res, seed: int, rnd: int, phase: int, q32: int) -> np.nda
     return legs.astype(np.uint8)
 
 
+LINK_DOWN = 0xFFFFFFFF  # GS_LINK_DOWN: the link carries nothing
+LEGS_NO_CONNECT = 255  # GS_LEGS_NO_CONNECT: the connect of that pair would fail
+MAX_ZONES = 16  # GS_MAX_ZONES
+
+
+def _link_matrix(link) -> np.ndarray:
+    link = np.asarray(link)
+    if link.ndim != 2 or link.shape[0] != link.shape[1] or not 1 <= link.shape[0] <= MAX_ZONES:
+        raise ValueError(f"link: a [Z, Z] matrix of 32-bit thresholds, 1 <= Z <= {MAX_ZONES} (got shape {link.shape})")
+    return link.astype(np.uint64)
+
+
+def connect_ok(ini, res, zone, link) -> np.ndarray:
+    """The connect rule of zoned links (include/gossip_sim.h): the exchange ``ini[e] -> res[e]`` is attempted iff
+    both nodes exist, both zone bytes are below Z and neither ``link[zone a][zone b]`` nor ``link[zone b][zone a]``
+    is ``LINK_DOWN``.  A link down in one direction alone fails the connects of both directions."""
+    link = _link_matrix(link)
+    Z = link.shape[0]
+    zone = np.asarray(zone, dtype=np.int64).reshape(-1)
+    n = zone.size
+    a = np.asarray(ini, dtype=np.int64).reshape(-1)
+    b = np.asarray(res, dtype=np.int64).reshape(-1)
+    ok = (a >= 0) & (a < n) & (b >= 0) & (b < n)
+    za, zb = zone[np.where(ok, a, 0)], zone[np.where(ok, b, 0)]
+    ok &= (za < Z) & (zb < Z)
+    za, zb = np.where(ok, za, 0), np.where(ok, zb, 0)
+    return ok & (link[za, zb] != LINK_DOWN) & (link[zb, za] != LINK_DOWN)
+
+
+def draw_cuts_zoned(ini, res, seed: int, rnd: int, phase: int, zone, link) -> np.ndarray:
+    """The definition of the zoned draw; the device's ``gs_draw_cuts_zoned`` must equal it.  Message m of an
+    attempted exchange (0 Syn a->b, 1 SynAck b->a, 2 Ack a->b) is lost iff word m of ``draw_cuts``' Philox block is
+    below the link threshold of that message's direction; a pair whose connect would fail gets 255."""
+    linkm = _link_matrix(link)
+    zone = np.asarray(zone, dtype=np.int64).reshape(-1)
+    a = np.asarray(ini, dtype=np.int64).reshape(-1)
+    b = np.asarray(res, dtype=np.int64).reshape(-1)
+    if a.shape != b.shape:
+        raise ValueError("initiators and responders differ in length")
+    n = a.size
+    ok = connect_ok(a, b, zone, linkm)
+    za, zb = zone[np.where(ok, a, 0)], zone[np.where(ok, b, 0)]
+    fwd, bwd = linkm[za, zb], linkm[zb, za]
+    full = lambda v: np.full(n, v & 0xFFFFFFFF, dtype=np.uint64)  # noqa: E731
+    w = philox4x32(full(rnd), a.astype(np.uint64) & _M32, b.astype(np.uint64) & _M32, full(phase),
+                   seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF)
+    legs = np.where(w[0] < fwd, 0, np.where(w[1] < bwd, 1, np.where(w[2] < fwd, 2, 3)))
+    return np.where(ok, legs, LEGS_NO_CONNECT).astype(np.uint8)
+
+
+def filter_targets_zoned(targets, zone, link) -> tuple[np.ndarray, int]:
+    """The mirror of ``gs_filter_targets_zoned``: ``targets`` ([N, slots], -1 = none: ``gs_select_peers``' output)
+    with every target whose connect would fail made -1, and the number of targets dropped."""
+    t = np.asarray(targets, dtype=np.int32)
+    n = np.asarray(zone).reshape(-1).size
+    if t.ndim != 2 or t.shape[0] != n:
+        raise ValueError(f"targets: [N, slots] for {n} nodes (got shape {t.shape})")
+    ini = np.repeat(np.arange(n, dtype=np.int64), t.shape[1])
+    drop = (t.reshape(-1) >= 0) & ~connect_ok(ini, t.reshape(-1), zone, link)
+    out = np.where(drop.reshape(t.shape), -1, t).astype(np.int32)
+    return out, int(drop.sum())
+
+
 def draw_cuts(ini, res, seed: int, rnd: int, phase: int, loss: float) -> np.ndarray:
     """uint8 legs of the exchanges ``ini[e] -> res[e]`` of phase ``phase`` of round ``rnd`` under independent
     message loss with probability ``loss``."""

@@ -44,6 +44,38 @@ def detect_rates(census: dict) -> dict:
     }
 
 
+def merge_censuses(parts: list[dict]) -> dict:
+    """Censuses of disjoint observer sets of one cluster (``GossipSim.detect_census_zoned``: one per component) as
+    one: what ``gs_detect_census`` defines for slices, but over rows -- sums add, ``observers`` among them, maxima
+    take the largest, the per-target counts add, the smallest time of death is the smallest and the largest the
+    largest (-1 = nobody), the per-row counts add (a row is counted in one part).  ``ShardGroup.detect_census``
+    merges over target columns instead (``observers`` taken once, per-target tensors joined), and all-reduces: the
+    two do not share code."""
+    from ._lib import DETECT_HIST_FIELDS, DETECT_MAX_FIELDS, DETECT_OVER_FIELDS, DETECT_TOTAL_FIELDS
+
+    if not parts:
+        raise ValueError("no census to merge")
+    out = {k: (max if k in DETECT_MAX_FIELDS else sum)(p[k] for p in parts) for k in DETECT_TOTAL_FIELDS}
+    for k in DETECT_HIST_FIELDS + DETECT_OVER_FIELDS:
+        out[k] = [sum(p[k][b] for p in parts) for b in range(len(parts[0][k]))]
+    out.update(detect_rates(out))
+    for k in ("target_live_by", "target_dead_by", "row_false_suspicions", "row_undetected"):
+        if k in parts[0]:
+            acc = parts[0][k].clone()
+            for p in parts[1:]:
+                acc += p[k]
+            out[k] = acc
+    if "target_first_tod" in parts[0]:
+        first, last = parts[0]["target_first_tod"].clone(), parts[0]["target_last_tod"].clone()
+        for p in parts[1:]:
+            f = p["target_first_tod"]
+            both = (first >= 0) & (f >= 0)
+            first = first.where(~both, first.minimum(f)).where(both | (first >= 0), f)
+            last = last.maximum(p["target_last_tod"])
+        out["target_first_tod"], out["target_last_tod"] = first, last
+    return out
+
+
 def roc(census: dict, thresholds) -> list[tuple[float, float, float]]:
     """``(threshold, up_over / up_phi, down_over / down_phi)`` per swept threshold: the share of the up targets'
     windows a detector with that ``phi_threshold`` would suspect (false suspicions) against the share of the down

@@ -19,6 +19,16 @@ With ``WorkloadSpec.frame_limit`` every phase is first sized by ``gs_traffic_cen
 ``rd["traffic_totals"] = True``, which reads each phase's totals back (one host wait per phase) and accumulates
 them in ``rd["traffic"]``; either of the two also sizes the phases of a round without ``frame_limit`` (nothing is
 refused then: the phase runs with the network's legs).  Without any of the three nothing changes.
+
+With ``WorkloadSpec.topology`` (``aiocluster_amd.topology``: zones and the links between them) and
+``WorkloadSpec.link_events`` the network is partitioned: ``prepare`` applies each round's events at its start, removes
+from every explicit phase the pairs whose connect would fail (``rd["exchanges"]`` counts the attempted exchanges,
+``rd["no_connect"]`` the rest), draws the legs of the others with the zoned mirror (``cuts.draw_cuts_zoned``; only in
+rounds in which some link loses messages) and keeps that round's link snapshot (``rd["topo"]``, ``rd["zone"]`` on the
+device, ``rd["link"]``).  With a ``PeerSelector`` ``run_round`` filters the selected targets on the device
+(``gs_filter_targets_zoned``) before the schedule, and draws every scheduled phase's legs with ``gs_draw_cuts_zoned``;
+``rd["no_connect"]`` is then the device's count, read once per round.  The zoned legs feed the traffic census exactly
+as the uniform ones do.  With no topology nothing changes.
 """
 
 from __future__ import annotations
@@ -49,10 +59,22 @@ def boot_ops(n: int, k: int) -> list[np.ndarray]:
 def prepare(spec, rounds: int, torch, dev) -> list[dict]:
     """Every round's device inputs (host schedule generation is not timed).  Write values are
     interned as ids 2^24 + i with the byte length of ``workload.write_value``."""
-    from .cuts import draw_cuts_q32, loss_q32
+    from .cuts import LINK_DOWN, draw_cuts_q32, draw_cuts_zoned, loss_q32
     from .workload import OP_DELETE, OP_DELETE_AFTER_TTL, Workload, liveness_tick, phase_tick, round_tick
 
     q32 = loss_q32(spec.loss)
+    topo = getattr(spec, "topology", None)
+    if topo is not None:
+        if q32:
+            raise ValueError("WorkloadSpec.loss together with a topology: express a uniform loss as a uniform link "
+                             "matrix")
+        if topo.n != spec.n:
+            raise ValueError(f"topology of {topo.n} nodes for a workload of {spec.n}")
+        topo = topo.copy()  # the events change the links: the spec keeps the initial ones
+        zone_dev = torch.from_numpy(topo.zone.copy()).to(dev)
+    elif getattr(spec, "link_events", None):
+        raise ValueError("WorkloadSpec.link_events without a topology")
+    events = sorted(getattr(spec, "link_events", None) or [], key=lambda e: e[0])
     wl = Workload(spec)
     out = []
     vid = 1 << 24
@@ -70,6 +92,16 @@ def prepare(spec, rounds: int, torch, dev) -> list[dict]:
             ops[dele, 3] = 0
             ops[dele, 4] = 0
         r = p.r
+        no_connect = 0
+        if topo is not None:
+            for _, action, args in (e for e in events if e[0] == r):
+                topo.apply(action, args)
+            kept = []
+            for a, b in p.phases:
+                ok = topo.connect_ok(a, b)
+                no_connect += int((~ok).sum())
+                kept.append((a[ok], b[ok]))
+            p.phases = kept
         out.append({
             "r": r,
             "t": round_tick(r),
@@ -86,6 +118,15 @@ def prepare(spec, rounds: int, torch, dev) -> list[dict]:
             out[-1]["legs"] = [torch.from_numpy(draw_cuts_q32(a, b, spec.cut_seed, r, i, q32)).to(dev)
                                for i, (a, b) in enumerate(p.phases)]
             out[-1]["loss_q32"], out[-1]["cut_seed"] = q32, spec.cut_seed
+        if topo is not None:
+            snap = topo.copy()
+            out[-1].update(no_connect=no_connect, topo=snap, zone=zone_dev, link=snap.link, cut_seed=spec.cut_seed)
+            # legs only in rounds in which some link loses messages (a round of whole and down links runs plain phases)
+            out[-1]["zoned_loss"] = bool(((snap.link != 0) & (snap.link != LINK_DOWN)).any())
+            if out[-1]["zoned_loss"]:
+                out[-1]["legs"] = [
+                    torch.from_numpy(draw_cuts_zoned(a, b, spec.cut_seed, r, i, snap.zone, snap.link)).to(dev)
+                    for i, (a, b) in enumerate(p.phases)]
         if getattr(spec, "frame_limit", False):
             out[-1]["frame_limit"] = True
     return out
@@ -163,7 +204,13 @@ def run_round(sims, rd, events=None, group=None, sel=None):
     phases = legs = None
     if sel is not None:
         sel.select(rd["up"], rd["r"])
+        dropped = None
+        if rd.get("topo") is not None:  # a failed connect occupies neither node: removed before the schedule
+            dropped = sims[0].torch.zeros(1, dtype=sims[0].torch.int32, device=sims[0].device)
+            sims[0].filter_targets(sel.targets, rd["zone"], rd["link"], dropped=dropped)
         ph, offs, left = sel.schedule(rd["up"], rd["r"])
+        if dropped is not None:
+            rd["no_connect"] = int(dropped.item())
         phases = [(a, b, n, phase_tick(rd["r"], p)) for p, (a, b, n) in enumerate(ph)]
         rd["exchanges"] = offs[-1]
         rd["unscheduled"] = left
@@ -171,6 +218,9 @@ def run_round(sims, rd, events=None, group=None, sel=None):
         rd["phases_run"] = len(phases)
         if rd.get("loss_q32"):  # message loss over the scheduled phases, drawn on the device
             legs = [sims[0].draw_cuts(a, b, rd["cut_seed"], rd["r"], p, rd["loss_q32"])
+                    for p, (a, b, n) in enumerate(ph)]
+        elif rd.get("zoned_loss"):  # ... per link, on the device
+            legs = [sims[0].draw_cuts_zoned(a, b, rd["cut_seed"], rd["r"], p, rd["zone"], rd["link"])
                     for p, (a, b, n) in enumerate(ph)]
     if rd["t_live"] >= rd["t"] + TICKS_PER_ROUND:
         raise ValueError(f"round {rd['r']}: liveness tick {rd['t_live']} reaches the next round's tick")

@@ -403,19 +403,21 @@ class ShardGroup:
         return out
 
     def detect_census(self, up, tick: int | None = None, down_since=None, thresholds=(), per_target: bool = False,
-                      per_row: bool = False) -> dict:
+                      per_row: bool = False, observers=None) -> dict:
         """``GossipSim.detect_census`` of the whole cluster: totals, histograms, ``up_over`` / ``down_over`` and
         the per-row counts summed over the slices (``observers`` taken once), maxima maxed, the per-target tensors
         joined along the target axis (each slice holds its own targets, so the smallest and largest times of death
         need no combining).  Over a ``DistComm`` the sums and maxima are all-reduced and the per-target parts
-        gathered, as ``view_census`` does."""
+        gathered, as ``view_census`` does.  ``observers``: as for ``GossipSim.detect_census`` (the rows counted,
+        apart from the targets' truth ``up``)."""
         import torch
 
         from ._lib import DETECT_HIST_FIELDS, DETECT_MAX_FIELDS, DETECT_OVER_FIELDS, DETECT_TOTAL_FIELDS
         from .detect import detect_rates
 
         thresholds = list(thresholds)
-        parts = [s.detect_census(up, tick, down_since, thresholds, per_target, per_row) for s in self.slices]
+        parts = [s.detect_census(up, tick, down_since, thresholds, per_target, per_row, observers=observers)
+                 for s in self.slices]
         sums = [k for k in DETECT_TOTAL_FIELDS if k not in DETECT_MAX_FIELDS and k != "observers"]
         lists = DETECT_HIST_FIELDS + DETECT_OVER_FIELDS
         vec = [sum(p[k] for p in parts) for k in sums]

@@ -448,6 +448,54 @@ class GossipSim:
                                       phase, loss_q32, C.c_void_p(out.data_ptr())), "gs_draw_cuts")
         return out
 
+    def _zone_args(self, zone, link):
+        """(device u8 zone tensor, host u32 [Z * Z] ctypes array, Z) of a ``topology.Topology`` -- or of a zone
+        array (host or device) with ``link`` the [Z, Z] matrix."""
+        if link is None:
+            zone, link = zone.zone, zone.link
+        lk = np.ascontiguousarray(np.asarray(link), dtype=np.uint32)
+        if lk.ndim != 2 or lk.shape[0] != lk.shape[1]:
+            raise GsError(f"link: a [Z, Z] matrix (got shape {lk.shape})")
+        z = zone if hasattr(zone, "data_ptr") else self._dev(np.asarray(zone, dtype=np.uint8), self.torch.uint8)
+        if z.dtype != self.torch.uint8 or int(z.numel()) != self.n:
+            raise GsError(f"zone: one uint8 per node (got {int(z.numel())} {z.dtype} for {self.n} nodes)")
+        return z, lk.ctypes.data_as(C.POINTER(C.c_uint32)), int(lk.shape[0]), lk
+
+    def draw_cuts_zoned(self, initiators, responders, seed: int, rnd: int, phase: int, zone, link=None, out=None):
+        """gs_draw_cuts_zoned: the device u8 legs of one phase under zoned links (``zone``: a ``Topology``, or a
+        zone array with ``link`` the [Z, Z] thresholds); 255 = the connect of that pair would fail.  The mirror is
+        ``cuts.draw_cuts_zoned``."""
+        ini, res = self._pairs_dev(initiators, responders)
+        n = int(ini.numel())
+        z, lp, Z, keep = self._zone_args(zone, link)
+        if out is None:
+            out = self.torch.empty(n, dtype=self.torch.uint8, device=self.device)
+        if n or self.sliced or not 1 <= Z <= _lib.GS_MAX_ZONES:
+            self._chk(self.L.gs_draw_cuts_zoned(self.h, C.c_void_p(ini.data_ptr()), C.c_void_p(res.data_ptr()), n, seed,
+                                                rnd, phase, C.c_void_p(z.data_ptr()), lp, Z,
+                                                C.c_void_p(out.data_ptr())), "gs_draw_cuts_zoned")
+        del keep
+        return out
+
+    def filter_targets(self, targets, zone, link=None, out=None, dropped=None):
+        """gs_filter_targets_zoned: ``targets`` (device int32 [N, slots]: ``PeerSelector.targets``) with every target
+        whose connect would fail made -1 (``out`` defaults to ``targets``: in place); ``dropped`` (device int32 [1])
+        is added to.  Asynchronous on the sim's stream.  The mirror is ``cuts.filter_targets_zoned``."""
+        torch = self.torch
+        if targets.dtype != torch.int32 or targets.dim() != 2 or int(targets.shape[0]) != self.n:
+            raise GsError(f"targets: a device int32 tensor [{self.n}, slots]")
+        if out is None:
+            out = targets
+        if out.dtype != torch.int32 or tuple(out.shape) != tuple(targets.shape):
+            raise GsError("out: a device int32 tensor shaped like targets")
+        z, lp, Z, keep = self._zone_args(zone, link)
+        self._chk(self.L.gs_filter_targets_zoned(self.h, C.c_void_p(targets.data_ptr()), C.c_void_p(out.data_ptr()),
+                                                 int(targets.numel()), C.c_void_p(z.data_ptr()), lp, Z,
+                                                 C.c_void_p(dropped.data_ptr()) if dropped is not None else None),
+                  "gs_filter_targets_zoned")
+        del keep
+        return out
+
     # ------------------------------------------------------- sliced phases (shards > 1)
     def phase_count(self, t: int, ini, res, out=None):
         """gs_phase_count: pass 1 on this slice; returns the device u64 slice totals [n, 2] (as int64)."""
@@ -654,7 +702,7 @@ class GossipSim:
         return out
 
     def detect_census(self, up, tick: int | None = None, down_since=None, thresholds=(), per_target: bool = False,
-                      per_row: bool = False) -> dict:
+                      per_row: bool = False, observers=None) -> dict:
         """gs_detect_census: what the failure detector makes of the cluster against the truth ``up``, in one
         read-only device pass (blocking).  Over the pairs (observer up, target != observer) of this handle's
         columns: ``up_pairs`` / ``up_live`` / ``up_dead`` / ``up_unknown`` and the same for down targets;
@@ -667,12 +715,19 @@ class GossipSim:
         exceeds ``thresholds[i]``.  Derived: ``false_suspicion_rate`` = up_dead / up_pairs, ``detected_fraction``
         = down_dead / down_pairs, ``undetected`` = down_live.  ``per_target`` adds the device int32 tensors
         ``target_live_by``, ``target_dead_by``, ``target_first_tod``, ``target_last_tod`` ([ncol]; -1 = nobody holds
-        it dead); ``per_row`` adds ``row_false_suspicions`` and ``row_undetected`` ([N])."""
+        it dead); ``per_row`` adds ``row_false_suspicions`` and ``row_undetected`` ([N]).  With ``observers``
+        (gs_detect_census_for) the rows counted are those with ``observers[o] != 0`` and ``up`` is the targets'
+        truth alone: one side of a partition against what it can reach (``detect_census_zoned``)."""
         self._flush()
-        if "gs_detect_census" in self.L.gs_missing:
-            raise GsError("gs_detect_census: this GS_LIB build lacks the entry point")
+        fn = "gs_detect_census" if observers is None else "gs_detect_census_for"
+        if fn in self.L.gs_missing:
+            raise GsError(f"{fn}: this GS_LIB build lacks the entry point")
         torch = self.torch
         u = up if hasattr(up, "data_ptr") else self._dev(np.asarray(up, dtype=np.uint8), torch.uint8)
+        ob = None
+        if observers is not None:
+            ob = (observers if hasattr(observers, "data_ptr")
+                  else self._dev(np.asarray(observers, dtype=np.uint8), torch.uint8))
         ds = None
         if down_since is not None:
             ds = (down_since if hasattr(down_since, "data_ptr")
@@ -683,12 +738,14 @@ class GossipSim:
         targets = torch.empty((4, self.ncol), dtype=torch.int32, device=self.device) if per_target else None
         rows = torch.empty((2, self.n), dtype=torch.int32, device=self.device) if per_row else None
         tot = _lib.GsDetectTotals()
-        self._chk(self.L.gs_detect_census(self.h, C.c_void_p(u.data_ptr()),
-                                          C.c_void_p(ds.data_ptr()) if ds is not None else None,
-                                          self.last_tick if tick is None else int(tick), ta if n else None, n,
-                                          C.c_void_p(targets.data_ptr()) if per_target else None,
-                                          C.c_void_p(rows.data_ptr()) if per_row else None, C.byref(tot)),
-                  "gs_detect_census")
+        tail = (C.c_void_p(ds.data_ptr()) if ds is not None else None, self.last_tick if tick is None else int(tick),
+                ta if n else None, n, C.c_void_p(targets.data_ptr()) if per_target else None,
+                C.c_void_p(rows.data_ptr()) if per_row else None, C.byref(tot))
+        if ob is None:
+            self._chk(self.L.gs_detect_census(self.h, C.c_void_p(u.data_ptr()), *tail), fn)
+        else:
+            self._chk(self.L.gs_detect_census_for(self.h, C.c_void_p(ob.data_ptr()), C.c_void_p(u.data_ptr()), *tail),
+                      fn)
         out = {k: int(getattr(tot, k)) for k in _lib.DETECT_TOTAL_FIELDS}
         for k in _lib.DETECT_HIST_FIELDS:
             out[k] = [int(x) for x in getattr(tot, k)]
@@ -700,6 +757,30 @@ class GossipSim:
              out["target_last_tod"]) = targets[0], targets[1], targets[2], targets[3]
         if per_row:
             out["row_false_suspicions"], out["row_undetected"] = rows[0], rows[1]
+        return out
+
+    def detect_census_zoned(self, up, topo, down_clock, link_clock, thresholds=(), tick: int | None = None,
+                            per_target: bool = False, per_row: bool = False, per_component: bool = False) -> dict:
+        """The detection census of a partitioned cluster, whose truth depends on the observer: target ``j`` is up
+        for observer ``o`` iff it is reachable (``topology.Topology.reachable``).  One gs_detect_census_for call per
+        component -- observers = the component's up nodes, up = its reachable targets, down_since = its
+        ``LinkClock.unreachable_since`` -- merged by ``detect.merge_censuses`` (sums add, maxima take the largest,
+        the smallest time of death the smallest, ``observers`` adds).  Rows that are not counted are not read, so the
+        calls together stream the matrix about once.  ``up`` is a host mask; ``down_clock`` a ``detect.DownClock``
+        (or its ``down_since``).  ``per_component`` adds ``components``: the per-component results, in
+        ``topo.components()`` order."""
+        from .detect import merge_censuses
+
+        up_h = np.asarray(up.cpu() if hasattr(up, "cpu") else up).astype(bool)
+        reach = topo.reachable(up_h)
+        since = link_clock.unreachable_since(topo, up_h, down_clock)
+        comp = topo.node_components()
+        parts = [self.detect_census(reach[c].astype(np.uint8), tick, since[c], thresholds, per_target, per_row,
+                                    observers=(up_h & (comp == c)).astype(np.uint8))
+                 for c in range(reach.shape[0])]
+        out = merge_censuses(parts)
+        if per_component:
+            out["components"] = parts
         return out
 
     def traffic_census(self, t: int, pairs, legs=None, frame_limit: bool = False, cluster_id: str = "default-cluster",

@@ -151,6 +151,13 @@ class WorkloadSpec:
     # the reference's frame limit (server.py:502-514): before every phase gs_traffic_census sizes its messages, and an
     # exchange stops where the peer would refuse an oversize packet (the phase runs with the census's legs_out)
     frame_limit: bool = False
+    # network partitions (aiocluster_amd.topology): the zones and initial links, and the link events
+    # [(round, action, args)] -- action one of Topology.apply's ("split", "heal_all", "cut", "heal", "set_link") --
+    # that take effect at that round's start.  The schedule itself does not change: driver.prepare removes the
+    # exchanges whose connect would fail and draws the rest's legs per link.  Not together with `loss` (a uniform
+    # loss is a uniform link matrix).
+    topology: object | None = None
+    link_events: list = field(default_factory=list)
     extra: dict = field(default_factory=dict)
 
 

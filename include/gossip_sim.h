@@ -330,6 +330,43 @@ int gs_run_phase_cut(gs_handle *h, const int32_t *initiators, const int32_t *res
  * < loss_q32; legs[e] (DEVICE u8[n]) = messages delivered before the first lost one.  loss_q32 = 0: all 3. */
 int gs_draw_cuts(gs_handle *h, const int32_t *initiators, const int32_t *responders, uint32_t n, uint64_t seed,
                  uint32_t round, uint32_t phase, uint32_t loss_q32, uint8_t *legs);
+
+/* Network partitions: zoned links.
+ *   Zones: every node has a zone, zone[j] in 0 .. Z-1 (DEVICE u8 [N], owned by the caller like `up`), 1 <= Z <=
+ *     GS_MAX_ZONES.
+ *   Links: link[x * Z + y] (HOST u32 [Z][Z]) = the loss threshold of a message sent from a node of zone x to a node of
+ *     zone y -- the diagonal is the loss inside a zone, the matrix need not be symmetric.  GS_LINK_DOWN: the link
+ *     carries nothing.  Any other value q is gs_draw_cuts' loss_q32: a message is lost iff its Philox word is < q.
+ *   Connect: an exchange a -> b is attempted only if neither link[zone a][zone b] nor link[zone b][zone a] is
+ *     GS_LINK_DOWN; otherwise the TCP connect times out (asyncio.wait_for(open_coro, connect_timeout),
+ *     server.py:403-405, 424-431) and nothing happens at either node -- the responder's inc_heartbeat of
+ *     server.py:524 does not run either.  Such an exchange is REMOVED before the phase runs (it is not legs 0).
+ *     Partial loss does not fail a connect: TCP retries it.
+ *   Messages: message m (0 Syn a->b, 1 SynAck b->a, 2 Ack a->b) of an attempted exchange is lost iff word m of
+ *     Philox4x32-10(key = seed, counter = (round, initiator, responder, phase)) -- gs_draw_cuts' counter -- is below
+ *     the link threshold of that message's direction.  With every entry of link equal to one q < GS_LINK_DOWN the
+ *     zoned draw equals gs_draw_cuts(..., q) byte for byte.
+ * gs_draw_cuts_zoned: legs[e] (DEVICE u8 [n]) = messages delivered before the first lost one, or GS_LEGS_NO_CONNECT
+ *   for a pair whose connect would fail, an initiator or responder >= N, or a zone byte >= Z.  gs_run_phase_cut
+ *   counts a value above 3 in err_bad_index and does nothing for that exchange: a caller that forgets to remove such
+ *   pairs is reported, never silently wrong.  Asynchronous on h's stream, no readback.
+ * gs_filter_targets_zoned: targets_in (DEVICE i32 [n_targets], gs_select_peers' output: entry o * (n_targets / N) +
+ *   slot is a target of node o, -1 = none; n_targets a multiple of N) copied to targets_out with every target whose
+ *   connect would fail (or that is >= N, or has a zone byte >= Z) replaced by -1; targets_out may alias targets_in.
+ *   *dropped (DEVICE u32, ADDED to; or NULL) counts them.  gs_schedule_phases then schedules only exchanges that will
+ *   be attempted: a failed connect occupies neither node (_gossip tasks run concurrently, server.py:476-493).
+ *   Asynchronous on h's stream.
+ * Both: GS_E_INVALID (checked before any device work; gs_last_error names the function) for a NULL argument
+ * (dropped excepted) or Z outside 1 .. GS_MAX_ZONES; GS_E_UNSUPPORTED on sliced handles, as gs_run_phase_cut. */
+#define GS_MAX_ZONES 16u
+#define GS_LINK_DOWN 0xFFFFFFFFu
+#define GS_LEGS_NO_CONNECT 255u
+int gs_draw_cuts_zoned(gs_handle *h, const int32_t *initiators, const int32_t *responders, uint32_t n, uint64_t seed,
+                       uint32_t round, uint32_t phase, const uint8_t *zone /*DEVICE [N]*/,
+                       const uint32_t *link /*HOST [Z][Z]*/, uint32_t Z, uint8_t *legs /*DEVICE [n]*/);
+int gs_filter_targets_zoned(gs_handle *h, const int32_t *targets_in, int32_t *targets_out, uint32_t n_targets,
+                            const uint8_t *zone /*DEVICE [N]*/, const uint32_t *link /*HOST [Z][Z]*/, uint32_t Z,
+                            uint32_t *dropped /*DEVICE, added to; or NULL*/);
 /* Owner-column sliced phase (n_shards > 1; gs_run_phase refuses sliced handles).  The slices of one
  * cluster run, per phase, on the same initiators/responders:
  *   1. gs_phase_count: pass 1 of every exchange on this slice's columns (heartbeats, failure-detector
@@ -563,6 +600,22 @@ int gs_detect_census(gs_handle *h, const uint8_t *up /*DEVICE [N]*/, const uint3
                      uint32_t tick, const double *thresholds /*HOST*/, uint32_t n_thresholds,
                      uint32_t *targets /*DEVICE [4][ncol] or NULL*/, uint32_t *rows /*DEVICE [2][N] or NULL*/,
                      gs_detect_totals *out /*HOST*/);
+/* gs_detect_census with the two roles of `up` separated: a row o is counted iff observers[o] != 0 (DEVICE u8 [N]),
+ * a target's truth is up[col_lo + j].  Everything else is gs_detect_census' contract word for word (outputs, slicing
+ * rules, refusals -- observers NULL is GS_E_INVALID too, and gs_last_error names gs_detect_census_for -- read-only,
+ * blocking); gs_detect_census is this call with observers == up.  The pair (o, o) is never counted, whichever truth
+ * up[o] gives.  Rows that are not counted are neither loaded nor reduced.
+ * A zoned census (truth = reachability: target j is reachable for observer o iff up[j] and the zones of o and j are
+ * joined by a chain of zones each consecutive pair of which has both directions not down) is one call per
+ * component: observers = up & (component of o == c), up = that component's reachable targets, down_since = that
+ * component's unreachable_since (the earliest tick of the causes still in force: the node went down, the two
+ * components were separated).  The calls together stream the matrix about once; their results merge as slices do,
+ * but over rows: sums add, maxima take the largest, the smallest tod the smallest, observers ADDS. */
+int gs_detect_census_for(gs_handle *h, const uint8_t *observers /*DEVICE [N]*/, const uint8_t *up /*DEVICE [N]*/,
+                         const uint32_t *down_since /*DEVICE [N] or NULL*/, uint32_t tick,
+                         const double *thresholds /*HOST*/, uint32_t n_thresholds,
+                         uint32_t *targets /*DEVICE [4][ncol] or NULL*/, uint32_t *rows /*DEVICE [2][N] or NULL*/,
+                         gs_detect_totals *out /*HOST*/);
 
 /* Traffic census: what a phase costs on the wire, and which of its frames the peer would refuse.  A read-only dry
  * run of the phase gs_run_phase_cut(h, initiators, responders, ., n, tick) would run, on the state as it stands: one
