@@ -4776,6 +4776,275 @@ __global__ __launch_bounds__(LB, 4) void k_view_census(Dev d, VcArgs a, uint32_t
             if (s_rows[i]) atomicAdd(&a.rows[o0 + i], s_rows[i]);
 }
 
+// Age census (gs_age_census): k_view_census's streaming pass over GS_R_MV, in ticks.  The caller's write log
+// wlog[ncol][WL] holds the tick at which each owner's max_version was first seen at each value (gs_note_writes); a
+// counted view at version v < M (M = the owner's own max_version) is behind, and its age is tick - wlog[j][v + 1],
+// the age of the oldest write its max_version does not cover (NONE there: counted in unlogged and nowhere else).
+// A pair the observer does not know (general layout) is a view at version 0.
+// The same workgroups as k_view_census: (band of VC_BAND rows, column chunk of LB x PER columns), one 16-byte
+// non-temporal load per thread and row, VC_AHEAD rows in flight, the owners' own versions loaded once.  In the
+// canonical 8-bit layout (SWAR) a row's 16 views are four words whose lags come out four at a time; a row with no
+// lag costs nothing more.  Only a view that is behind gathers its log entry: a row's gathers are issued together,
+// before any is used, and a chunk's log rows are shared by the whole band (and by the bands beside it), so they
+// come from L2.  Over the band a thread keeps, per column, the largest lag (= the smallest version seen, the
+// column's floor: one atomicMin per (band, column), none when it equals M), the age histogram as packed fields of
+// VC_HBITS bits, and the maxima; a row's largest age takes one wave reduction and one atomic per (row, chunk).
+// All results are integer sums, minima and maxima: they do not depend on scheduling.
+enum AcSlot {
+    AC_OBS = 0, AC_UNK, AC_BEHIND, AC_UNLOG, AC_MAXAGE, AC_SPREAD, AC_PENDING, AC_UNLOG_W, AC_MAXSPREAD, AC_MAXPEND,
+    AC_AH, AC_SH = AC_AH + GS_VC_BUCKETS, AC_PH = AC_SH + GS_VC_BUCKETS, AC_NUM = AC_PH + GS_VC_BUCKETS
+};
+struct AcArgs {
+    const uint8_t *up;         // nullptr: every row counts
+    const uint32_t *wlog;      // [ncol][WL]
+    uint32_t WL, tick;
+    unsigned long long *acc;   // [AC_NUM], zeroed
+    uint32_t *floor;           // [ncol], preset to the owners' own max_version
+    uint32_t *rows;            // optional, zeroed
+    uint32_t *done;            // optional, in/out (k_age_owners)
+};
+template <bool SWAR>
+__global__ __launch_bounds__(LB, 4) void k_age_census(Dev d, AcArgs a, uint32_t chunks) {
+    constexpr uint32_t PER = SWAR ? 16u : 8u;  // views per thread and row (k_view_census)
+    __shared__ uint32_t s_hist[GS_VC_BUCKETS];
+    __shared__ uint32_t s_rows[VC_BAND];
+    __shared__ uint32_t s_M[SWAR ? 16 : 1][LB];  // SWAR: the owners' full max_version, read only for views behind
+    const bool genm = !(d.flags & GS_CANONICAL);
+    const uint32_t tid = threadIdx.x;
+    const uint32_t rb = blockIdx.x / chunks, cb = blockIdx.x % chunks;
+    const uint32_t j0 = cb * LB * PER + tid * PER;
+    const uint32_t o0 = rb * VC_BAND, nrow = min(VC_BAND, d.N - o0);
+    const bool act = j0 < d.ncol;
+    const uint32_t nvt = act ? min(d.ncol - j0, PER) : 0u;  // this thread's real columns
+    for (uint32_t i = tid; i < GS_VC_BUCKETS; i += LB) s_hist[i] = 0u;
+    for (uint32_t i = tid; i < VC_BAND; i += LB) s_rows[i] = 0u;
+    uint32_t owm7v[4], vm7v[4];   // SWAR: four columns per word
+    uint32_t ownM[SWAR ? 1 : 8];  // per column
+#pragma unroll
+    for (uint32_t q = 0; q < PER / 4u; q++) {
+        const uint32_t jq = j0 + 4u * q;
+        uint32_t M[4] = {0u, 0u, 0u, 0u};
+        if (jq < d.ncol) ld4(d.self_mv + jq, M);
+        if constexpr (SWAR) {
+            owm7v[q] = (M[0] & 0x7Fu) | ((M[1] & 0x7Fu) << 8) | ((M[2] & 0x7Fu) << 16) | ((M[3] & 0x7Fu) << 24);
+            const uint32_t nv = jq < d.ncol ? min(d.ncol - jq, 4u) : 0u;
+            vm7v[q] = nv >= 4u ? B7 : B7 & ((1u << (8u * nv)) - 1u);  // bit 7 of the real columns
+#pragma unroll
+            for (uint32_t i = 0; i < 4; i++) s_M[4u * q + i][tid] = M[i];  // (read back by this thread only)
+        } else {
+#pragma unroll
+            for (uint32_t i = 0; i < 4; i++) ownM[4u * q + i] = M[i];
+        }
+    }
+    __syncthreads();
+    v4u_t bm[VC_AHEAD];
+    auto ldv = [&](uint32_t o, v4u_t &nm) {
+        nm = v4u_t{0u, 0u, 0u, 0u};
+        if (!act) return;
+        const size_t p0 = pix(d, o, j0);
+        const uint8_t *m8 = reinterpret_cast<const uint8_t *>(d.mv);
+        if (SWAR) {
+            nm = __builtin_nontemporal_load(reinterpret_cast<const v4u_t *>(m8 + p0));
+        } else if (d.mv8) {
+            const v2u_t x = __builtin_nontemporal_load(reinterpret_cast<const v2u_t *>(m8 + p0));
+            nm.x = x.x; nm.y = x.y;
+        } else {
+            nm = __builtin_nontemporal_load(reinterpret_cast<const v4u_t *>(d.mv + p0));
+        }
+    };
+#pragma unroll
+    for (uint32_t u = 0; u < VC_AHEAD; u++) ldv(o0 + min(u, nrow - 1u), bm[u]);
+    uint32_t t_unk = 0, t_beh = 0, t_unlog = 0, t_maxage = 0, n_obs = 0;
+    uint32_t mxl[SWAR ? 4 : 8];  // the largest lag per column over the band (SWAR: as bytes)
+#pragma unroll
+    for (uint32_t k = 0; k < (SWAR ? 4u : 8u); k++) mxl[k] = 0u;
+    unsigned long long ah[5] = {0ull, 0ull, 0ull, 0ull, 0ull};  // bucket b: field b & 3 of ah[b >> 2]
+    // the views of one row that are behind, lag[k] != 0: gather their log entries together, then count them
+    auto ages = [&](const uint32_t (&lag)[PER], uint32_t &rowm) {
+        uint32_t e[PER];
+#pragma unroll
+        for (uint32_t k = 0; k < PER; k++) {
+            e[k] = NONE;
+            if (!lag[k]) continue;
+            uint32_t Mk;
+            if constexpr (SWAR) Mk = s_M[k][tid];
+            else Mk = ownM[k];
+            const uint32_t w = Mk - lag[k] + 1u;  // the oldest write the view lacks (1 <= w <= M)
+            if (w < a.WL) e[k] = a.wlog[(size_t)(j0 + k) * a.WL + w];
+        }
+#pragma unroll
+        for (uint32_t k = 0; k < PER; k++) {
+            if (!lag[k]) continue;
+            t_beh++;
+            if (e[k] == NONE) { t_unlog++; continue; }
+            const uint32_t age = a.tick - e[k];
+            rowm = max(rowm, age);
+            const uint32_t b = vc_bucket(age);
+            const unsigned long long inc = 1ull << (VC_HBITS * (b & 3u));
+#pragma unroll
+            for (uint32_t g = 0; g < 5u; g++) ah[g] += (b >> 2) == g ? inc : 0ull;
+        }
+    };
+    auto row = [&](uint32_t r, const v4u_t mr) {
+        const uint32_t o = o0 + r;
+        if (a.up && !a.up[o]) return;
+        n_obs++;
+        uint32_t rowm = 0;  // this thread's largest age in the row
+        if (act) {
+            const uint32_t mw[4] = {mr.x, mr.y, mr.z, mr.w};
+            uint32_t lag[PER];
+            if constexpr (SWAR) {
+                uint32_t lagM[4], any = 0u;
+#pragma unroll
+                for (uint32_t q = 0; q < 4u; q++) {
+                    lagM[q] = ((owm7v[q] | B7) - (mw[q] & L7)) & L7 & bytes7(vm7v[q]);  // (own - view) mod 2^7
+                    any |= lagM[q];
+                }
+                if (any) {
+#pragma unroll
+                    for (uint32_t q = 0; q < 4u; q++) {
+                        mxl[q] = bmax7(mxl[q], lagM[q]);
+#pragma unroll
+                        for (uint32_t i = 0; i < 4; i++) lag[4u * q + i] = (lagM[q] >> (8u * i)) & 0x7Fu;
+                    }
+                    ages(lag, rowm);
+                }
+            } else {
+                const size_t p0 = pix(d, o, j0);
+                uint32_t ps[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
+                if (genm) {
+                    const uint4 x = *reinterpret_cast<const uint4 *>(d.pos + p0), y = *reinterpret_cast<const uint4 *>(d.pos + p0 + 4);
+                    ps[0] = x.x; ps[1] = x.y; ps[2] = x.z; ps[3] = x.w; ps[4] = y.x; ps[5] = y.y; ps[6] = y.z; ps[7] = y.w;
+                }
+                uint32_t any = 0u;
+#pragma unroll
+                for (uint32_t k = 0; k < 8u; k++) {
+                    lag[k] = 0u;
+                    if (k >= nvt) continue;
+                    uint32_t v = 0u;  // a pair the observer does not know: a view at version 0
+                    if (genm && ps[k] == NONE) {
+                        t_unk++;
+                    } else {
+                        const uint32_t w = d.mv8 ? mv_dec8((mw[k >> 2] >> (8u * (k & 3u))) & 0xFFu, ownM[SWAR ? 0 : k])
+                                                 : (mw[k >> 1] >> (16u * (k & 1u))) & 0xFFFFu;
+                        v = w & MV_MASK;
+                    }
+                    lag[k] = ownM[SWAR ? 0 : k] - v;
+                    mxl[SWAR ? 0 : k] = max(mxl[SWAR ? 0 : k], lag[k]);
+                    any |= lag[k];
+                }
+                if (any) ages(lag, rowm);
+            }
+        }
+        t_maxage = max(t_maxage, rowm);
+        if (a.rows && __ballot(rowm != 0u)) {  // one wave reduction; one global atomic per (row, chunk) below
+            const uint32_t m = wave_max32(rowm);
+            if ((tid & 63u) == 0u) atomicMax(&s_rows[r], m);
+        }
+    };
+    for (uint32_t r0 = 0; r0 < nrow; r0 += VC_AHEAD) {
+#pragma unroll
+        for (uint32_t u = 0; u < VC_AHEAD; u++) {
+            const uint32_t r = r0 + u;
+            if (r >= nrow) break;
+            const v4u_t mr = bm[u];
+            ldv(o0 + min(r + VC_AHEAD, nrow - 1u), bm[u]);  // (past the band: the last row again, unused)
+            row(r, mr);
+        }
+    }
+    // the band's results: at most one atomicMin per column, none where no counted view is behind
+#pragma unroll
+    for (uint32_t k = 0; k < PER; k++) {
+        if (k >= nvt) continue;
+        uint32_t lk, Mk;
+        if constexpr (SWAR) {
+            lk = (mxl[k >> 2] >> (8u * (k & 3u))) & 0x7Fu;
+            Mk = s_M[k][tid];
+        } else {
+            lk = mxl[SWAR ? 0 : k];
+            Mk = ownM[SWAR ? 0 : k];
+        }
+        if (lk) atomicMin(&a.floor[j0 + k], Mk - lk);
+    }
+#pragma unroll
+    for (uint32_t b = 0; b < GS_VC_BUCKETS; b++) {
+        const uint32_t c = (uint32_t)(ah[b >> 2] >> (VC_HBITS * (b & 3u))) & ((1u << VC_HBITS) - 1u);
+        if (c) atomicAdd(&s_hist[b], c);
+    }
+    {
+        const unsigned long long su = wave_sum(t_unk), sb = wave_sum(t_beh), sl = wave_sum(t_unlog);
+        const uint32_t ma = wave_max32(t_maxage);
+        if ((tid & 63u) == 0u) {
+            if (su) atomicAdd(&a.acc[AC_UNK], su);
+            if (sb) atomicAdd(&a.acc[AC_BEHIND], sb);
+            if (sl) atomicAdd(&a.acc[AC_UNLOG], sl);
+            if (ma) atomicMax(&a.acc[AC_MAXAGE], (unsigned long long)ma);
+        }
+    }
+    if (cb == 0 && tid == 0 && n_obs) atomicAdd(&a.acc[AC_OBS], (unsigned long long)n_obs);
+    __syncthreads();
+    for (uint32_t i = tid; i < GS_VC_BUCKETS; i += LB)
+        if (s_hist[i]) atomicAdd(&a.acc[AC_AH + i], (unsigned long long)s_hist[i]);
+    if (a.rows)
+        for (uint32_t i = tid; i < nrow; i += LB)
+            if (s_rows[i]) atomicMax(&a.rows[o0 + i], s_rows[i]);
+}
+
+// The owner pass of gs_age_census, one thread per owner column, after k_age_census (nothing with no counted observer).
+// f = the column's floor, d0 = done[j] (f without done): the versions in (d0, f] have now reached every counted observer
+// (credited once: done[j] = max(d0, f)); those in (max(d0, f), M] are not yet everywhere.
+__global__ __launch_bounds__(LB) void k_age_owners(Dev d, AcArgs a) {
+    __shared__ uint32_t s_h[2][GS_VC_BUCKETS];
+    __shared__ uint32_t s_mx[2];
+    for (uint32_t i = threadIdx.x; i < 2u * GS_VC_BUCKETS; i += LB) (&s_h[0][0])[i] = 0u;
+    if (threadIdx.x < 2u) s_mx[threadIdx.x] = 0u;
+    __syncthreads();
+    const uint32_t j = blockIdx.x * LB + threadIdx.x;
+    uint32_t n_spread = 0, n_pend = 0, n_unlog = 0;
+    if (j < d.ncol && a.acc[AC_OBS]) {
+        const uint32_t *wl = a.wlog + (size_t)j * a.WL;
+        const uint32_t M = min(d.self_mv[j], a.WL - 1u), f = min(a.floor[j], M);
+        const uint32_t d0 = a.done ? a.done[j] : f, top = max(d0, f);
+        for (uint32_t w = d0 + 1u; w <= f; w++) {  // (runs only with done)
+            const uint32_t e = wl[w];
+            if (e == NONE) { n_unlog++; continue; }
+            n_spread++;
+            atomicAdd(&s_h[0][vc_bucket(a.tick - e)], 1u);
+            atomicMax(&s_mx[0], a.tick - e);
+        }
+        if (a.done && f > d0) a.done[j] = f;
+        for (uint32_t w = top + 1u; w <= M; w++) {
+            const uint32_t e = wl[w];
+            if (e == NONE) { n_unlog++; continue; }
+            n_pend++;
+            atomicAdd(&s_h[1][vc_bucket(a.tick - e)], 1u);
+            atomicMax(&s_mx[1], a.tick - e);
+        }
+    }
+    const unsigned long long ss = wave_sum(n_spread), sp = wave_sum(n_pend), su = wave_sum(n_unlog);
+    if ((threadIdx.x & 63u) == 0u) {
+        if (ss) atomicAdd(&a.acc[AC_SPREAD], ss);
+        if (sp) atomicAdd(&a.acc[AC_PENDING], sp);
+        if (su) atomicAdd(&a.acc[AC_UNLOG_W], su);
+    }
+    __syncthreads();
+    for (uint32_t i = threadIdx.x; i < 2u * GS_VC_BUCKETS; i += LB) {
+        const uint32_t c = (&s_h[0][0])[i];
+        if (c) atomicAdd(&a.acc[AC_SH + i], (unsigned long long)c);
+    }
+    if (threadIdx.x < 2u && s_mx[threadIdx.x]) atomicMax(&a.acc[AC_MAXSPREAD + threadIdx.x], (unsigned long long)s_mx[threadIdx.x]);
+}
+
+// gs_note_writes: the tick at which each owner's max_version was first seen at its current value
+__global__ __launch_bounds__(LB) void k_note_writes(Dev d, uint32_t *wlog, uint32_t WL, uint32_t tick) {
+    const uint32_t j = blockIdx.x * LB + threadIdx.x;
+    if (j >= d.ncol) return;
+    const uint32_t v = d.self_mv[j];
+    if (!v || v >= WL) return;
+    uint32_t *e = wlog + (size_t)j * WL + v;
+    if (*e == NONE) *e = tick;
+}
+
 // Detection census (gs_detect_census): a read-only streaming pass over GS_R_FD_STATE -- and, with thresholds (PHI),
 // over GS_R_FD_LAST and GS_R_FD -- that counts, over the pairs (observer o up, target j != o), the live / dead /
 // unknown pairs by whether the target is up, the detection latencies (time of death - down_since), the ages of
@@ -6492,6 +6761,7 @@ struct gs_handle {
     unsigned long long *vc_buf = nullptr;  // gs_view_census scratch: VC_NUM u64 accumulators, then the probes
     std::vector<uint64_t> vc_img;          // ... and its host image (the upload before, the read after the pass)
     unsigned long long *dc_buf = nullptr;  // gs_detect_census scratch: DC_NUM u64 accumulators
+    unsigned long long *ac_buf = nullptr;  // gs_age_census scratch: AC_NUM u64 accumulators, then the floor u32 [ncol]
     unsigned long long *tc_buf = nullptr;  // gs_traffic_census scratch: NSHARD rows of TC_NUM u64 accumulators
     hipStream_t hside = nullptr;    // k_pack_heavy's stream (forked after the lite slot work, joined after the packer)
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
@@ -7107,6 +7377,7 @@ void gs_destroy(gs_handle *h) {
     if (h->sm_buf) (void)hipFree(h->sm_buf);
     if (h->vc_buf) (void)hipFree(h->vc_buf);
     if (h->dc_buf) (void)hipFree(h->dc_buf);
+    if (h->ac_buf) (void)hipFree(h->ac_buf);
     if (h->tc_buf) (void)hipFree(h->tc_buf);
     if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
     if (h->ev_join) (void)hipEventDestroy(h->ev_join);
@@ -8457,6 +8728,95 @@ int gs_detect_census_for(gs_handle *h, const uint8_t *observers, const uint8_t *
                          gs_detect_totals *out) {
     return detect_census(h, "gs_detect_census_for", observers, up, down_since, tick, thresholds, n_thresholds, targets,
                          rows, out);
+}
+
+static_assert(sizeof(gs_age_totals) == 80 * 8, "gs_age_totals layout");
+
+int gs_write_log_words(const gs_handle *h, uint32_t *wl) {
+    if (!h || !wl) return GS_E_INVALID;
+    *wl = round_up(h->K * (h->C - 1) + 1, 4);  // GS_R_VLOG's row: versions 1 .. K (C - 1)
+    return GS_OK;
+}
+
+int gs_write_log_init(gs_handle *h, uint32_t *wlog) {
+    if (!h) return GS_E_INVALID;
+    if (!wlog) return fail(h, GS_E_INVALID, "gs_write_log_init: wlog is NULL");
+    uint32_t WL = 0;
+    gs_write_log_words(h, &WL);
+    HIPCHK(h, hipMemsetAsync(wlog, 0xFF, (size_t)h->ncol * WL * 4, h->stream));
+    return GS_OK;
+}
+
+int gs_note_writes(gs_handle *h, uint32_t tick, uint32_t *wlog) {
+    if (!h) return GS_E_INVALID;
+    if (!wlog) return fail(h, GS_E_INVALID, "gs_note_writes: wlog is NULL");
+    if (!h->booted) return fail(h, GS_E_INVALID, "gs_note_writes: not booted");
+    uint32_t WL = 0;
+    gs_write_log_words(h, &WL);
+    k_note_writes<<<(h->ncol + LB - 1) / LB, LB, 0, h->stream>>>(h->d, wlog, WL, tick);
+    HIPCHK(h, hipGetLastError());
+    return GS_OK;
+}
+
+int gs_age_census(gs_handle *h, const uint8_t *up, const uint32_t *wlog, uint32_t tick, uint32_t flags, uint32_t *floor,
+                  uint32_t *rows, uint32_t *done, gs_age_totals *out) {
+    if (!h) return GS_E_INVALID;
+    if (!wlog) return fail(h, GS_E_INVALID, "gs_age_census: wlog is NULL");
+    if (!out) return fail(h, GS_E_INVALID, "gs_age_census: out is NULL");
+    if (flags) return fail(h, GS_E_INVALID, "gs_age_census: unknown flags 0x%x", flags);
+    if ((int32_t)(tick - h->max_tick) < 0 || tick - h->max_tick >= FD_OLD_AGE)
+        return fail(h, GS_E_INVALID, "gs_age_census: tick %u is before the handle's latest tick %u, or 2^15 or more "
+                    "past it", tick, h->max_tick);
+    if (!h->booted) return fail(h, GS_E_INVALID, "gs_age_census: not booted");
+    const size_t bytes = (size_t)AC_NUM * 8 + (size_t)h->ncol * 4;
+    if (!h->ac_buf) HIPCHK(h, hipMalloc(&h->ac_buf, bytes));
+    hipStream_t s = h->stream;
+    AcArgs a;
+    a.up = up;
+    a.wlog = wlog;
+    gs_write_log_words(h, &a.WL);
+    a.tick = tick;
+    a.acc = h->ac_buf;
+    a.floor = reinterpret_cast<uint32_t *>(h->ac_buf + AC_NUM);
+    a.rows = rows;
+    a.done = done;
+    const Dev &d = h->d;
+    HIPCHK(h, hipMemsetAsync(h->ac_buf, 0, (size_t)AC_NUM * 8, s));
+    // a column's floor starts at the owner's own max_version: the value with no counted observer, or none behind
+    HIPCHK(h, hipMemcpyAsync(a.floor, d.self_mv, (size_t)h->ncol * 4, hipMemcpyDeviceToDevice, s));
+    if (rows) HIPCHK(h, hipMemsetAsync(rows, 0, (size_t)h->N * 4, s));
+    const bool swar = (d.flags & GS_CANONICAL) && d.mv8;
+    const uint32_t per = swar ? 16u : 8u, chunks = (h->ncol + LB * per - 1) / (LB * per);
+    const uint32_t grid = (h->N + VC_BAND - 1) / VC_BAND * chunks;
+    if (swar)
+        k_age_census<true><<<grid, LB, 0, s>>>(d, a, chunks);
+    else
+        k_age_census<false><<<grid, LB, 0, s>>>(d, a, chunks);
+    HIPCHK(h, hipGetLastError());
+    k_age_owners<<<(h->ncol + LB - 1) / LB, LB, 0, s>>>(d, a);
+    HIPCHK(h, hipGetLastError());
+    if (floor) HIPCHK(h, hipMemcpyAsync(floor, a.floor, (size_t)h->ncol * 4, hipMemcpyDeviceToDevice, s));
+    uint64_t acc[AC_NUM];
+    HIPCHK(h, hipMemcpyAsync(acc, h->ac_buf, sizeof acc, hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipStreamSynchronize(s));
+    memset(out, 0, sizeof *out);
+    out->observers = acc[AC_OBS];
+    out->pairs = out->observers * h->ncol;
+    out->unknown = acc[AC_UNK];
+    out->behind = acc[AC_BEHIND];
+    out->unlogged = acc[AC_UNLOG];
+    out->max_age = acc[AC_MAXAGE];
+    out->spread_writes = acc[AC_SPREAD];
+    out->pending_writes = acc[AC_PENDING];
+    out->unlogged_writes = acc[AC_UNLOG_W];
+    out->max_spread_latency = acc[AC_MAXSPREAD];
+    out->max_pending_age = acc[AC_MAXPEND];
+    for (uint32_t b = 0; b < GS_AC_BUCKETS; b++) {
+        out->age_hist[b] = acc[AC_AH + b];
+        out->spread_hist[b] = acc[AC_SH + b];
+        out->pending_age_hist[b] = acc[AC_PH + b];
+    }
+    return GS_OK;
 }
 
 static_assert(sizeof(gs_traffic_totals) == TC_NUM * 8, "gs_traffic_totals layout");

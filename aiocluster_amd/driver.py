@@ -29,6 +29,10 @@ device, ``rd["link"]``).  With a ``PeerSelector`` ``run_round`` filters the sele
 (``gs_filter_targets_zoned``) before the schedule, and draws every scheduled phase's legs with ``gs_draw_cuts_zoned``;
 ``rd["no_connect"]`` is then the device's count, read once per round.  The zoned legs feed the traffic census exactly
 as the uniform ones do.  With no topology nothing changes.
+
+On a sim created with ``write_log=True`` ``begin`` notes the round's writes in the sim's write log at the round's tick
+(``gs_note_writes`` after its ``gs_owner_writes``), which is what ``GossipSim.age_census`` ages views against.  Without
+the log nothing changes.
 """
 
 from __future__ import annotations
@@ -138,6 +142,8 @@ def begin(sims, rd):
         if rd["nops"]:
             sim._chk(sim.L.gs_owner_writes(sim.h, C.c_void_p(rd["ops"].data_ptr()), rd["nops"], rd["t"]),
                      "gs_owner_writes")
+            if getattr(sim, "wlog", None) is not None:  # write_log=True: the round's writes are logged at its tick
+                sim.note_writes(rd["t"])
         sim._chk(sim.L.gs_begin_round(sim.h, C.c_void_p(rd["up"].data_ptr()), rd["t"]), "gs_begin_round")
 
 

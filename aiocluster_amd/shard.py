@@ -402,6 +402,56 @@ class ShardGroup:
             out["row_stale"] = t
         return out
 
+    def age_census(self, up=None, tick: int | None = None, per_owner: bool = False, per_row: bool = False,
+                   spread: bool = True) -> dict:
+        """``GossipSim.age_census`` of the whole cluster (slices created with ``write_log=True``; each keeps its own
+        columns' log and ``age_done``): totals and histograms summed over the slices (``observers`` taken once),
+        maxima maxed -- ``row_max_age`` too, a row's largest age over all columns --, ``owner_floor`` joined along the
+        owner axis.  Over a ``DistComm`` the sums and maxima are all-reduced and the parts gathered, as
+        ``view_census`` does."""
+        import torch
+
+        from ._lib import AGE_HIST_FIELDS, AGE_MAX_FIELDS, AGE_TOTAL_FIELDS
+
+        parts = [s.age_census(up, tick, per_owner, per_row, spread) for s in self.slices]
+        sums = [k for k in AGE_TOTAL_FIELDS if k not in AGE_MAX_FIELDS and k != "observers"]
+        vec = [sum(p[k] for p in parts) for k in sums]
+        for k in AGE_HIST_FIELDS:
+            vec += [sum(p[k][b] for p in parts) for b in range(len(parts[0][k]))]
+        mx = [max(p[k] for p in parts) for k in AGE_MAX_FIELDS]
+        dist = isinstance(self.comm, DistComm)
+        dev = self.slices[0].device
+        if dist:
+            d = self.comm.dist
+            cdev = "cpu" if d.get_backend(self.comm.group) == "gloo" else dev
+            v = torch.tensor(vec, dtype=torch.int64, device=cdev)
+            m = torch.tensor(mx, dtype=torch.int64, device=cdev)
+            d.all_reduce(v, group=self.comm.group)
+            d.all_reduce(m, op=d.ReduceOp.MAX, group=self.comm.group)
+            vec, mx = [int(x) for x in v.tolist()], [int(x) for x in m.tolist()]
+        out = {"observers": parts[0]["observers"]}
+        it = iter(vec)
+        out.update((k, next(it)) for k in sums)
+        out.update(zip(AGE_MAX_FIELDS, mx))
+        out = {k: out[k] for k in AGE_TOTAL_FIELDS}
+        for k in AGE_HIST_FIELDS:
+            out[k] = [next(it) for _ in parts[0][k]]
+        if per_owner:
+            t = torch.cat([p["owner_floor"] for p in parts])
+            if dist:  # slices differ in width (the last one is shorter): gathered padded to the widest
+                blk = _slice_block(self.n, self.comm.world)
+                pad = torch.zeros(blk, dtype=t.dtype, device=t.device)
+                pad[: t.numel()] = t
+                allp = self.comm.gather([pad])
+                t = torch.cat([allp[g, : min(blk, self.n - g * blk)] for g in range(self.comm.world)])
+            out["owner_floor"] = t
+        if per_row:
+            t = torch.stack([p["row_max_age"] for p in parts]).amax(0)
+            if dist:
+                t = self.comm.gather([t]).amax(0)
+            out["row_max_age"] = t
+        return out
+
     def detect_census(self, up, tick: int | None = None, down_since=None, thresholds=(), per_target: bool = False,
                       per_row: bool = False, observers=None) -> dict:
         """``GossipSim.detect_census`` of the whole cluster: totals, histograms, ``up_over`` / ``down_over`` and

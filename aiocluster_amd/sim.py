@@ -207,7 +207,8 @@ class GossipSim:
                  tombstones: bool = True, fd_ring: bool | None = None, hist_cap: int = 64,
                  nid_sizes: list[int] | None = None, initial_ops: list[np.ndarray] | None = None,
                  canonical: bool | None = None, shards: int = 1, shard: int = 0, held: bool = True,
-                 ring_rows=None, hb8: bool = False, mv8: bool = False, sliced: bool = False, esc_cols: int | None = None):
+                 ring_rows=None, hb8: bool = False, mv8: bool = False, sliced: bool = False, esc_cols: int | None = None,
+                 write_log: bool = False):
         import torch
 
         if not torch.cuda.is_available():
@@ -305,6 +306,17 @@ class GossipSim:
         self._ev_ord = 0
         self.last_tick = 0
         self.q9_events: list = []
+        # the write log (gs_note_writes): created before the boot writes, so that they are logged at their tick
+        self.wlog = self.age_done = None
+        if write_log:
+            from .staleness import alloc_log
+
+            wl = C.c_uint32()
+            self._chk(self.L.gs_write_log_words(h, C.byref(wl)), "gs_write_log_words")
+            self.wlog_words = int(wl.value)
+            self.wlog = alloc_log(torch, self.device, self.ncol, self.wlog_words)
+            self._chk(self.L.gs_write_log_init(h, C.c_void_p(self.wlog.data_ptr())), "gs_write_log_init")
+            self.age_done = torch.zeros(self.ncol, dtype=torch.int32, device=self.device)  # age_census(spread=True)
         if initial_values:
             for j in range(n):
                 for kk, v in initial_values.get(j, []):
@@ -391,11 +403,20 @@ class GossipSim:
             raise GsError("owner_writes: owners must be distinct within one batch")
         d = self._dev(ops.view(np.int32), self.torch.int32)
         self._chk(self.L.gs_owner_writes(self.h, C.c_void_p(d.data_ptr()), len(ops), tick), "gs_owner_writes")
+        if self.wlog is not None:
+            self.note_writes(tick)
         if self._ev is not None:  # gs_set_events: op i of this call has seq = ops issued before + i
             if order is None:
                 order = list(range(self._ev_writes, self._ev_writes + len(ops)))
                 self._ev_writes += len(ops)
             self._ev_wmap += list(order)
+
+    def note_writes(self, tick: int):
+        """gs_note_writes: log, at ``tick``, every owner version of this handle's columns not logged yet
+        (asynchronous; after each gs_owner_writes batch).  Needs ``write_log=True``."""
+        if self.wlog is None:
+            raise GsError("note_writes: the sim was created without write_log=True")
+        self._chk(self.L.gs_note_writes(self.h, int(tick), C.c_void_p(self.wlog.data_ptr())), "gs_note_writes")
 
     # --------------------------------------------------------------- round driver
     def begin_round(self, t: int, up):
@@ -699,6 +720,45 @@ class GossipSim:
             out["owner_behind"], out["owner_unknown"], out["owner_max_lag"] = owners[0], owners[1], owners[2]
         if per_row:
             out["row_stale"] = rows
+        return out
+
+    def age_census(self, up=None, tick: int | None = None, per_owner: bool = False, per_row: bool = False,
+                   spread: bool = True) -> dict:
+        """gs_age_census: how stale the views are, in ticks, and how long writes take to reach every node, in one
+        read-only device pass (blocking; needs ``write_log=True``).  Over the observer rows with ``up[o] != 0``
+        (default: all) and this handle's owner columns, at ``tick`` (default: the handle's latest tick):
+        ``observers``, ``pairs``, ``unknown``, ``behind`` (views whose max_version is below the owner's own),
+        ``unlogged`` (behind on a version nobody noted), ``max_age`` and ``age_hist`` (20 buckets in ticks: 0, then
+        2^(b-1) <= x < 2^b) of tick - the tick of the oldest write the view's max_version does not cover.  With
+        ``spread`` the sim's ``age_done`` vector is updated: ``spread_writes`` = the writes this call found at every
+        counted observer for the first time, with ``spread_hist`` / ``max_spread_latency``; ``pending_writes``,
+        ``pending_age_hist``, ``max_pending_age`` = the writes not yet everywhere (without ``spread``: those above
+        the floor).  ``per_owner`` adds the device int32 tensor ``owner_floor`` ([ncol]: the smallest version any
+        counted observer holds), ``per_row`` adds ``row_max_age`` ([N])."""
+        if self.wlog is None:
+            raise GsError("age_census: the sim was created without write_log=True")
+        self._flush()
+        torch = self.torch
+        u = None
+        if up is not None:
+            u = up if hasattr(up, "data_ptr") else self._dev(np.asarray(up, dtype=np.uint8), torch.uint8)
+        floor = torch.empty(self.ncol, dtype=torch.int32, device=self.device) if per_owner else None
+        rows = torch.empty(self.n, dtype=torch.int32, device=self.device) if per_row else None
+        tot = _lib.GsAgeTotals()
+        self._chk(self.L.gs_age_census(self.h, C.c_void_p(u.data_ptr()) if u is not None else None,
+                                       C.c_void_p(self.wlog.data_ptr()),
+                                       self.latest_tick() if tick is None else int(tick), 0,
+                                       C.c_void_p(floor.data_ptr()) if per_owner else None,
+                                       C.c_void_p(rows.data_ptr()) if per_row else None,
+                                       C.c_void_p(self.age_done.data_ptr()) if spread else None, C.byref(tot)),
+                  "gs_age_census")
+        out = {k: int(getattr(tot, k)) for k in _lib.AGE_TOTAL_FIELDS}
+        for k in _lib.AGE_HIST_FIELDS:
+            out[k] = [int(x) for x in getattr(tot, k)]
+        if per_owner:
+            out["owner_floor"] = floor
+        if per_row:
+            out["row_max_age"] = rows
         return out
 
     def detect_census(self, up, tick: int | None = None, down_since=None, thresholds=(), per_target: bool = False,

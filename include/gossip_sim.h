@@ -547,6 +547,62 @@ int gs_view_census(gs_handle *h, const uint8_t *up /*DEVICE or NULL*/, uint32_t 
                    uint32_t *rows /*DEVICE [N] or NULL: per observer, this handle's owner columns it is behind on or does not know; 0 for rows not counted*/,
                    gs_view_totals *out /*HOST*/);
 
+/* Age census: how stale the views are in ticks, and how long a write takes to reach every node.
+ * The write log: u32 wlog[n_cols][WL], DEVICE memory owned by the caller (like `owners` and `rows` of the censuses; it
+ *   is no region), WL = gs_write_log_words = n_keys * (hist_cap - 1) + 1 rounded up to 4 (GS_R_VLOG's row length:
+ *   versions never exceed K (C - 1)).  Entry [jl][v] = the tick at which owner column jl's own max_version was first
+ *   seen equal to v, GS_NONE = never seen; entry 0 is unused.  Every effective owner write raises the owner's
+ *   max_version by exactly one (state.py:137-180); a same-value set, a delete of an absent key and the like leave it.
+ *   gs_write_log_init fills the log with GS_NONE.  gs_note_writes(tick): for every owner column of this handle (a slice
+ *   logs its own), v = GS_R_SELF_MV[jl]; if v > 0 and wlog[jl][v] == GS_NONE it becomes `tick`.  Called after each
+ *   gs_owner_writes batch (owners are distinct per batch: at most one version per owner per call) it logs every new
+ *   version and leaves no-ops alone; it reads no ops.  Both are asynchronous on the handle's stream.  A version whose
+ *   batch was not followed by a call stays GS_NONE: the census counts it apart (unlogged) and never guesses.
+ * gs_age_census, the pair pass: k_view_census' streaming pass over GS_R_MV, over the observer rows with up[o] != 0
+ *   (DEVICE u8 [N]; NULL: all rows) and this handle's owner columns.  A view's version v is its decoded max_version
+ *   (GS_MV_INEXACT ignored); a pair the observer does not know (general layout: GS_R_POS == GS_NONE) is a view at
+ *   version 0.  The pair is behind iff v < M = GS_R_SELF_MV[jl]; its age is tick - wlog[jl][v + 1], the age of the
+ *   oldest write its max_version does not cover (a view with holes may lack older writes too: the definition goes by
+ *   max_version alone, as the view census' lag does).  If that entry is GS_NONE the pair is counted in `unlogged` and in
+ *   no histogram or maximum.  floor[jl] (DEVICE u32 [n_cols] or NULL) = the smallest v over the counted observers, M
+ *   with none; rows[o] (DEVICE u32 [N] or NULL) = the largest age in row o, 0 for a row not counted or behind nowhere.
+ * The owner pass, one thread per column, nothing with observers == 0 (its totals are zero, done untouched): f =
+ *   floor[jl], d = done ? done[jl] : f.  With done (DEVICE u32 [n_cols], in/out): every version w in (d, f] has now
+ *   reached every counted observer -- its latency tick - wlog[jl][w] goes to spread_hist, spread_writes and
+ *   max_spread_latency -- then done[jl] = max(d, f): a write is credited once, at the first census that finds it
+ *   everywhere, and a node that comes back behind later does not un-credit it.  Every w in (max(d, f), M] is a write
+ *   not yet everywhere: pending_writes, pending_age_hist, max_pending_age.  A GS_NONE entry met in either loop counts in
+ *   unlogged_writes only.  Latencies are quantised to the ticks at which the census is called, and "every node" is the
+ *   caller's `up`.
+ * Blocking; every output is overwritten (done is updated); no region and no field of gs_read_counters changes.  Sliced
+ * handles count their own columns: sums add over the slices, maxima take the largest, observers is the same in each.
+ * GS_E_INVALID (checked before any device work; gs_last_error names gs_age_census): h, wlog or out NULL; unknown flag
+ * bits (none is defined); tick below gs_latest_tick, or 2^15 or more past it. */
+#define GS_AC_BUCKETS 20u          /* ticks; GS_VC_BUCKETS' rule */
+typedef struct gs_age_totals {     /* all u64, 80 words */
+    uint64_t observers;            /* rows counted */
+    uint64_t pairs;                /* counted (observer, owner) pairs: observers x n_cols */
+    uint64_t unknown;              /* ... the observer does not know (views at version 0) */
+    uint64_t behind;               /* ... with v < M */
+    uint64_t unlogged;             /* behind pairs whose log entry is GS_NONE (in no histogram or maximum) */
+    uint64_t max_age;              /* ticks */
+    uint64_t spread_writes;        /* writes credited by this call (done != NULL) */
+    uint64_t pending_writes;       /* writes not yet at every counted observer */
+    uint64_t unlogged_writes;      /* GS_NONE entries met by the owner pass */
+    uint64_t max_spread_latency, max_pending_age;   /* ticks */
+    uint64_t age_hist[GS_AC_BUCKETS];           /* sums to behind - unlogged */
+    uint64_t spread_hist[GS_AC_BUCKETS];        /* sums to spread_writes */
+    uint64_t pending_age_hist[GS_AC_BUCKETS];   /* sums to pending_writes */
+    uint64_t reserved[9];                       /* 11 fields + 3 x 20 + 9 = 80 words */
+} gs_age_totals;
+int gs_write_log_words(const gs_handle *h, uint32_t *wl);
+int gs_write_log_init(gs_handle *h, uint32_t *wlog /*DEVICE [n_cols][WL]*/);
+int gs_note_writes(gs_handle *h, uint32_t tick, uint32_t *wlog /*DEVICE [n_cols][WL]*/);
+int gs_age_census(gs_handle *h, const uint8_t *up /*DEVICE [N] or NULL: all rows*/, const uint32_t *wlog,
+                  uint32_t tick, uint32_t flags /*0*/, uint32_t *floor /*DEVICE [n_cols] or NULL*/,
+                  uint32_t *rows /*DEVICE [N] or NULL*/, uint32_t *done /*DEVICE [n_cols], in/out, or NULL*/,
+                  gs_age_totals *out /*HOST*/);
+
 /* Detection census: what the failure detector makes of the cluster, against the caller's ground truth.  One
  * read-only streaming pass over GS_R_FD_STATE (GS_R_FD_TOD for the dead pairs; with thresholds also GS_R_FD_LAST and
  * GS_R_FD).  It stands in for FailureDetector.live_nodes / dead_nodes / phi of every observer
