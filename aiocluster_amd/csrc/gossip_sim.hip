@@ -27,36 +27,18 @@
 //   owner writes      state.py:124-180
 //   failure detector  failure_detector.py:12-128
 
-#include <hip/hip_runtime.h>
-#include <rccl/rccl.h>
-
-#include <cstdarg>
-#include <cstdlib>
-#include <cstdio>
-#include <algorithm>
-#include <cstring>
-#include <string>
-#include <vector>
-#include <type_traits>
-
-#include "../../include/gossip_sim.h"
+#include "gossip_common.h"
 
 namespace {
 
-constexpr uint32_t NONE = GS_NONE;
-constexpr int WAVE = 64;
 constexpr int XB = 128;  // exchange workgroup: 2 waves
 #ifndef XB_WAVES
 #define XB_WAVES 4  // waves per SIMD k_exchange is compiled for (VGPR budget 512 / 4 = 128)
 #endif
-constexpr int LB = 256;  // liveness / elementwise workgroups
 #ifndef LIVE_PER
 #define LIVE_PER 64  // 1024-column chunks per k_liveness workgroup, at most (r4g/h/k/p at 65,536: 64 -> 10.5-10.8 ms, 32 -> 10.7-11.2, 16 -> 11.0-11.1, 8 -> 11.9, 4 -> 13.6)
 #endif
 constexpr int NSHARD = 64;
-// native vectors: the nontemporal load / store builtins take them (not HIP's uint4 struct)
-typedef unsigned int v4u_t __attribute__((ext_vector_type(4)));
-typedef unsigned int v2u_t __attribute__((ext_vector_type(2)));
 constexpr uint32_t WIN = 16 * 64;  // positions per packer window (16 per lane)
 // KW of the kernels for K > 16 keys (up to 64).  Those instantiations take most of the build time; a
 // development build with -DGS_KW4_ONLY (tools/build_dev.sh) leaves them out and refuses K > 16.
@@ -67,7 +49,6 @@ constexpr int KWB = 16;
 #endif
 constexpr uint32_t NPL = GS_PLANES;  // report bit planes per observer row (phases per plane base)
 static_assert(NPL == 16 || NPL == 32, "k_liveness stages 16 or 32 planes");
-constexpr double TICK_S = 1.0 / 64.0;
 constexpr uint32_t HB_LAG_CHECK_EVERY = 1u << 14;  // round starts + phases between heartbeat-lag sweeps
 constexpr uint32_t HB8_LAG_CHECK_EVERY = 1u << 6;  // ... with GS_HB8 (checked before every round start and phase)
 constexpr uint32_t MV8_LAG_CHECK_EVERY = 1u << 5;  // GS_MV8: gs_owner_writes calls between max_version lag sweeps
@@ -85,117 +66,6 @@ static_assert(C_NUM <= CROW, "counter region");
 static_assert(C_CUT < CFIELDS, "gs_counters fields");
 static_assert(sizeof(gs_counters) == CFIELDS * 8, "gs_counters layout");
 
-struct Dev {
-    uint32_t N, NP, K, KP, C, mtu, flags, W;
-    // owner-column slice: this handle holds columns [col_lo, col_lo + ncol) of every observer row
-    // (NP = ncol rounded to 64 is the row stride); shards = 1: the whole matrix
-    uint32_t col_lo, ncol, shards, shard;
-    uint32_t max_iv, tomb_grace, dead_grace, sched_delay, lb_min, sum_bits;
-    uint32_t ablate;  // profiling only (env GS_ABLATE): 1 = skip packing, 2 = skip pass-1 stores (results invalid);
-                      // A/B, results valid: 8 = k_pass1v without its slow-group slots
-    double phi_thr, prior5;
-    double prior5t;  // prior5 in ticks (x 64): the liveness sweep's division-free phi test
-    float phi_thr_f, prior5t_f;  // the same in binary32: the sweep's first, full-rate test (2^-20 margin)
-    uint16_t *hb;       // heartbeat mod 2^16 (hb_dec: exact while a view lags its owner by < 2^16)
-    uint32_t *self_hb;  // [NP] each owner column's own heartbeat, full width
-    uint32_t *gc;
-    uint16_t *mv;  // max_version | MV_INEXACT (u16: versions <= K * (C - 1) <= 16,256)
-    uint8_t *held;
-    uint32_t *fd;       // sampling window: _sum in ticks | intervals appended since the last reset << sum_bits
-    uint16_t *fd_last;  // _last_heartbeat tick mod 2^16 (decoded against the operation's tick: fd_get)
-    uint8_t *fd_state;  // bits 0-1: 0 unknown, 1 live, 2 dead (_live_nodes / _dead_nodes); FD_WIN, FD_OLD
-    uint32_t *tod;      // time of death of a dead pair (read only for rows whose row word 2 has passed)
-    uint32_t *ts;
-    uint16_t *ring;
-    uint32_t *pos, *ord, *row;
-    uint8_t *last_w;
-    uint64_t *hist;  // version | meta << 32
-    uint32_t *lat;   // [NC][KP] each key's latest write: version | DeltaPb bytes of its kv << 16 (prefix views)
-    uint32_t *hist_vid;
-    uint16_t *nid_size;
-    uint8_t *key_len;
-    uint32_t *stamp;
-    unsigned long long *ctr;
-    uint32_t *sbits;  // sharded phases: stale-owner bitmaps of both directions per exchange [e][2][NP/32]
-    uint2 *cand;       // split phases: stale-owner records [e][dir][half][GS_CAND_CAP] (GS_R_CAND)
-    uint32_t *cand_n;  // [e][dir][half] stale owners found (GS_R_CAND_N)
-    // heartbeat reports of the current round not yet applied to the windows: one bit plane per phase
-    // p (tick t_round + 1 + p) and observer row, [N][NPL][PW] u64 in quad-interleaved column order
-    // (plane_word/plane_bit); a plane row is valid only if pstamp[o][p] holds that phase's tick
-    uint64_t *pend;
-    uint32_t *pstamp;  // [N][NPL]
-    uint32_t PW;       // u64 words per plane row: NP rounded up to 256, / 64
-    // plane base: the tick of the last gs_begin_round, or, once a round has run phases more than NPL
-    // ticks after it (the planes were replayed into the windows mid-round), the tick before the
-    // first phase after that replay; plane p holds the phase at tick t_round + 1 + p
-    uint32_t t_round;
-    // sub-phases (round 6): several phases at one tick -- every exchange select_nodes_for_gossip chose, however
-    // many phases its hubs need (server.py:476-493).  Plane p of the base holds the phase of VIRTUAL tick
-    // v_round + 1 + p (pstamp holds virtual ticks, unique over the handle's life) at real tick
-    // min(t_round + 1 + p, t_cap) (plane_tick); vt = the virtual tick of the phase being launched (set per phase by
-    // the host).  Without sub-phases v_round = t_round, vt = the phase's tick and t_cap = NONE: the round-5 layout.
-    uint32_t v_round, vt, t_cap;
-    // speculative max-version merge (canonical record phases): pass 1 already wrote
-    // max(sender, receiver) into the receiver's max_version word of every recorded candidate whose two
-    // views are prefix views; the packers restore the receiver's word of such a candidate when it is not
-    // sent, and skip the store when it is sent whole.  Set per phase by the host (gs_run_phase /
-    // gs_phase_count), identical in every kernel of the phase.
-    uint32_t spec;
-    uint4 *slot_stat;  // sliced phases: per (exchange, direction) {NodeDeltas, kvs, candidates, needs a pack}
-    // sampled rings (gs_config.ring_rows): ring slot of each observer row (NONE: a compact row), GS_R_RING
-    // then holds [ring_rows][NP][W]; nullptr otherwise
-    uint32_t *ring_slot;
-    // prefix views: each owner's writes by version, [NC][VL] (GS_R_VLOG): DeltaPb bytes of the kv field |
-    // version of the next write of the same key (0xFFFF: none) << 16 -- a prefix candidate's NodeDelta
-    // size from the entries (mr, ms] alone (pack_lite)
-    uint32_t *vlog;
-    uint32_t VL;
-    uint32_t lite;  // this phase runs k_lite before the exact packer (set per phase by the host)
-    uint32_t hb8;   // GS_HB8: hb holds u8 views (mod 2^8), else u16 (mod 2^16)
-    uint32_t mv8;   // GS_MV8: mv holds u8 views (version mod 2^7 | inexact << 7), else u16 words
-    uint32_t *self_mv;  // [NP] each owner column's own max_version (GS_R_SELF_MV)
-    // GS_MV8: [NP] both owner values packed for pass 1 (self_pack): one 16-byte load per 4 columns decodes
-    // both 8-bit views -- the heartbeat needs only R mod 2^8 and whether R is 0 (R < 2^15 kept exactly),
-    // the max_version word only M (< 2^15)
-    uint32_t *self_pk;
-    // GS_MV8 (pass 1 of the record phases, k_pass1v): per 16-owner group, bits 0-15 = "owner j's own heartbeat
-    // is < 2^8" (an 8-bit view of it stored as 0 is then the heartbeat 0), bits 16-31 = "owner j is hot": at the
-    // last lag sweep some view of j lagged by >= HOT_HB heartbeats or HOT_MV versions (GS_R_P1FLAGS)
-    uint32_t *p1flags;
-    uint32_t pl16;  // report planes in the 16-column layout of k_pass1v (plane16_bit), else the ballot layout
-    // the launch after a k_pass1v phase (k_pack_slice / k_settle<1>, set per launch by the host) first sets the
-    // phase's responders' small bits (k_p1v_fix's work, round 5: one launch fewer per phase)
-    uint32_t p1fix;
-    // escaped owner columns (gs_config.esc_cols, k_pass1v handles): EC slots of 16-bit views [N][EC]; esc_slot[j] =
-    // the slot of column j or NONE; esc_owner[s] = the column of slot s or NONE; esc_req = the sweep's scratch
-    // (columns to escape, bitmap [NP/32], then the move count and list)
-    uint16_t *esc16;
-    uint32_t *esc_slot, *esc_owner, *esc_req;
-    uint32_t EC;
-    // event stream (gs_set_events): records {observer, owner, key | kind << 8, old version, new version,
-    // tick, seq, phase}; kind 0 = on_key_change, 1 = node join, 2 = node leave; seq orders them, phase = ev_phase
-    // in apply_delta's records and 0 in every other (gossip_sim.h, gs_set_events).  ev == nullptr: off
-    uint32_t *ev, *ev_count;
-    uint32_t ev_cap;
-    uint32_t ev_phase;  // phases started on this handle since gs_set_events, this one included (1 = the first)
-    // the exact packer's heavy slots (round 6): k_pack_slice lists a slot with more than heavy_t stale owners here
-    // ([0] = count, then slot ids) instead of walking it, and k_pack_heavy packs it with a workgroup of its own;
-    // nullptr: no hand-off (set per launch by the host, one-slice record phases only)
-    uint32_t *heavy;
-    uint32_t heavy_t;
-    // one-slice prefix-view handles (round 6): sm[c] = the smallest possible NodeDelta of any owner column >= c --
-    // min over j >= c of msgf(msgf(NodeIdPb bytes of j) + 2 + the smallest kv field j ever wrote, GS_R_VLOG entry
-    // 0), a lower bound of every candidate's min1 -- rebuilt after every gs_owner_writes (k_sm_local, k_sm_fix); sm[ncol] =
-    // 0xFFFF.  First-fit continuation stops as soon as the budget left is below sm at the next candidate's column:
-    // no later candidate can add a NodeDelta (R only shrinks).  nullptr: not built (sliced handles: the chain's
-    // later slices hold the other columns)
-    uint16_t *sm;
-    uint32_t ev_wseq;  // owner-write ops issued since gs_set_events (the seq of the next call's op 0)
-    // cut exchanges (gs_run_phase_cut): legs[e] = messages delivered of exchange e; read by the CUT instantiations
-    // of the phase kernels only, which the host launches when it is set (set per phase; nullptr otherwise)
-    const uint8_t *legs;
-};
-
 // ------------------------------------------------------------------ protobuf sizes
 // proto3 wire sizes for messages.proto:39-74 (all field numbers < 16: one-byte tags).
 __host__ __device__ inline uint32_t vlen(uint32_t x) {
@@ -205,7 +75,6 @@ __host__ __device__ inline uint32_t ufield(uint32_t x) { return x ? 1u + vlen(x)
 __host__ __device__ inline uint32_t sfield(uint32_t n) { return n ? 1u + vlen(n) + n : 0u; }
 __host__ __device__ inline uint32_t msgf(uint32_t n) { return 1u + vlen(n) + n; }
 
-__device__ inline size_t pix(const Dev &d, uint32_t o, uint32_t j) { return (size_t)o * d.NP + j; }
 // the real tick of report plane p of the current plane base (sub-phases share the tick t_cap)
 __device__ inline uint32_t plane_tick(const Dev &d, uint32_t p) { return min(d.t_round + 1u + p, d.t_cap); }
 __device__ inline size_t hix(const Dev &d, uint32_t j, uint32_t w, uint32_t k) {
@@ -223,59 +92,21 @@ __device__ inline uint32_t make_meta(uint32_t kvlen, uint32_t status, uint32_t v
 __device__ inline bool is_sched(uint32_t dt, uint32_t t, uint32_t delay) {
     return dt != NONE && (t - dt) >= delay;
 }
-// FD_STATE byte: membership in bits 0-1 (FD_MEMB), FD_WIN = the pair has a sampling window (its
-// _last_heartbeat is set), FD_OLD = that last report is >= FD_OLD_AGE ticks old (k_fd_age)
-enum FdSt { FD_UNKNOWN = 0, FD_LIVE = 1, FD_DEAD = 2, FD_MEMB = 3, FD_WIN = 4, FD_OLD = 8 };
-constexpr uint32_t FD_OLD_AGE = 1u << 15;
 __device__ inline uint32_t dead_tod(const Dev &d, size_t p) {
     return (d.fd_state[p] & FD_MEMB) == FD_DEAD ? d.tod[p] : NONE;
 }
 
-// One sampling window (SamplingWindow + BoundedArrayStats, failure_detector.py:12-53, 131-162) per pair
-// in 6 bytes + 2 state bits: the _last_heartbeat tick mod 2^16 (GS_R_FD_LAST) and one word (GS_R_FD) =
-// _sum in ticks (sum_bits wide, exact: every interval is a whole number of 1/64 s) | intervals appended
-// since the last reset << sum_bits.  Decoding the tick against the operation's tick t is exact while the
-// report is < 2^16 ticks old; k_fd_age marks windows FD_OLD once it is 2^15 old (the host runs it at
-// least every 2^14 ticks), and an FD_OLD window's tick only ever enters as "more than max_interval
-// ago" (no interval appended, gs_create: max_interval < 2^14) and "phi above the threshold" (gs_create:
-// threshold x max(max_interval, prior) < 2^15), so it is decoded as t - 2^15.
-struct Fd {
-    uint32_t last, sum, cnt;  // last = NONE when there is no window
-};
-__device__ inline Fd fd_get(const Dev &d, uint32_t st, uint32_t l16, uint32_t sc, uint32_t t) {
-    const uint32_t last = !(st & FD_WIN) ? NONE : (st & FD_OLD) ? t - FD_OLD_AGE : t - ((t - l16) & 0xFFFFu);
-    return Fd{last, sc & ((1u << d.sum_bits) - 1u), sc >> d.sum_bits};
-}
 __device__ inline uint32_t fd_sc(const Dev &d, const Fd &f) { return f.sum | (f.cnt << d.sum_bits); }
 // the state byte after storing f (a window from its first report on; its tick is current again)
 __device__ inline uint32_t fd_st(uint32_t st, const Fd &f) {
     return f.last == NONE ? (st & ~(uint32_t)(FD_WIN | FD_OLD)) : ((st | FD_WIN) & ~(uint32_t)FD_OLD);
 }
 
-__device__ inline int lane_id() { return (int)__lane_id(); }
 // pass 1's row halves (one wave each; candidate lists per half): columns [0, H) and [H, ncol), H a multiple of
 // the pass's step -- 256 columns (k_pass1: 4 per lane) or 1024 (k_pass1v: 16 per lane)
 __device__ inline uint32_t half_cols(const Dev &d) {
     const uint32_t m = d.pl16 ? 1023u : 255u;
     return ((d.ncol + 1u) / 2u + m) & ~m;
-}
-
-__device__ inline bool bit(const uint32_t *bm, uint32_t j) { return (bm[j >> 5] >> (j & 31u)) & 1u; }
-
-__device__ inline uint32_t wave_incl_scan(uint32_t x) {
-    const int l = lane_id();
-#pragma unroll
-    for (int dd = 1; dd < WAVE; dd <<= 1) {
-        const uint32_t y = __shfl_up(x, dd, WAVE);
-        if (l >= dd) x += y;
-    }
-    return x;
-}
-
-__device__ inline unsigned long long wave_sum(unsigned long long x) {
-#pragma unroll
-    for (int dd = 32; dd >= 1; dd >>= 1) x += __shfl_xor(x, dd, WAVE);
-    return x;
 }
 
 __device__ inline void shard_add(const Dev &d, int c, unsigned long long v) {
@@ -356,14 +187,7 @@ __device__ inline void set_byte(uint32_t *w, int q, uint32_t v) {
 // history and GS_R_HELD is not read (nor kept) for it.  Exchanges between two such views need
 // only their max_versions and the owner's latest-write table (a hot 16-entry row per owner).
 constexpr uint32_t MV_INEXACT = GS_MV_INEXACT;
-constexpr uint32_t MV_MASK = GS_MV_INEXACT - 1u;
 
-// GS_MV8: a view's max_version in one byte, version mod 2^7 | MV_INEXACT >> 8, decoded against the owner's
-// own max_version M (every view is <= M; exact while it lags M by < 2^7: k_hb_lag) into the u16 word form
-// (version | MV_INEXACT) every consumer uses.  mv_word / mv_put: one view, either width.
-__device__ __forceinline__ uint32_t mv_dec8(uint32_t s, uint32_t M) {
-    return (M - ((M - (s & 0x7Fu)) & 0x7Fu)) | ((s & 0x80u) << 8);
-}
 __device__ __forceinline__ uint32_t mv_enc8(uint32_t w) { return (w & 0x7Fu) | ((w >> 8) & 0x80u); }
 // GS_R_SELF_PK: Rx = R mod 2^15 | (R >= 2^15) << 15 is congruent to R mod 2^8 and is 0 iff R is, and
 // every 8-bit view decodes to Rx - lag (lag < 2^8 <= Rx unless Rx = R < 2^15): the same order and the same
@@ -1376,10 +1200,6 @@ struct Grp {
 __device__ inline uint32_t plane_word(uint32_t c) { return (c >> 8) * 4u + (c & 3u); }
 __device__ inline uint32_t plane_bit(uint32_t c) { return (c >> 2) & 63u; }
 
-__device__ __forceinline__ void ld4(const uint32_t *p, uint32_t (&v)[4]) {
-    const uint4 x = *reinterpret_cast<const uint4 *>(p);
-    v[0] = x.x; v[1] = x.y; v[2] = x.z; v[3] = x.w;
-}
 // Heartbeats are stored mod 2^16 and decoded against the owner's own heartbeat R (every view of
 // owner j is <= R, and views lag R by < 2^16: DESIGN.md §3), so H = R - ((R - s) mod 2^16).
 __device__ __forceinline__ uint32_t hb_dec(uint32_t s, uint32_t R) { return R - ((R - s) & 0xFFFFu); }
@@ -1977,7 +1797,6 @@ __device__ __forceinline__ bool line_any_v(bool p) {
 #ifndef P1V_WAVES
 #define P1V_WAVES 5  // waves per SIMD k_pass1v is compiled for (r4i: 5 -> 2.19 ms per phase, 6 -> 2.25)
 #endif
-constexpr uint32_t B7 = 0x80808080u, L7 = 0x7F7F7F7Fu;
 // the 16-column plane layout: plane u16 g holds columns 16 g .. 16 g + 15, column 16 g + 4 q + i at bit 4 i + q
 __device__ __forceinline__ uint32_t plane16_bit(uint32_t c) { return 4u * (c & 3u) + ((c >> 2) & 3u); }
 // bit 7 of byte i of w[q] -> bit 4 i + q (the plane layout of one lane's 16 columns)
@@ -1996,18 +1815,6 @@ __device__ __forceinline__ uint32_t spread7(uint32_t n) { return ((n * 0x204081u
 // bit i of a nibble -> bit 4 i
 __device__ __forceinline__ uint32_t spread4(uint32_t n) {
     return (n & 1u) | ((n & 2u) << 3) | ((n & 4u) << 6) | ((n & 8u) << 9);
-}
-// per-byte (x - y) mod 2^8
-__device__ __forceinline__ uint32_t bsub(uint32_t x, uint32_t y) { return ((x | B7) - (y & L7)) ^ (~(x ^ y) & B7); }
-// wave-wide inclusive prefix sum (DPP: row shifts, then the row broadcasts)
-__device__ __forceinline__ uint32_t wave_scan_dpp(uint32_t x) {
-    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x111, 0xF, 0xF, false);  // row_shr:1
-    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x112, 0xF, 0xF, false);  // row_shr:2
-    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x114, 0xF, 0xF, false);  // row_shr:4
-    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x118, 0xF, 0xF, false);  // row_shr:8
-    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x142, 0xA, 0xF, false);  // row_bcast:15
-    x += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)x, 0x143, 0xC, 0xF, false);  // row_bcast:31
-    return x;
 }
 
 // A direction's stale owners of one step (mask words: bit 7 of byte i of word q = column c + 4 q + i) go out as
@@ -4423,944 +4230,6 @@ __global__ __launch_bounds__(LB) void k_hot_clear(Dev d) {
     if (i < d.NP / 16u) d.p1flags[i] &= 0xFFFFu;
 }
 
-// Dissemination census (gs_view_census): a read-only streaming pass over GS_R_MV (and, with GS_VC_HEARTBEATS,
-// GS_R_HB) that counts, over the observer rows with up[o] != 0, the known / unknown / behind / inexact views, the
-// version- and heartbeat-lag histograms and maxima, per owner column {behind, unknown, max version lag}, per
-// observer row the columns it is behind on or does not know, and the reach of up to GS_VC_MAX_PROBES
-// (owner, version) probes.
-// One workgroup per (band of VC_BAND consecutive observer rows, column chunk of LB x PER columns), as k_hb_lag:
-// one 16-byte non-temporal load per thread, row and region, VC_AHEAD rows in flight while one is reduced; the
-// owners' own values, escape slots and the probes are loaded once per workgroup.  Everything a thread counts stays
-// in registers over the band (per-owner counts, packed histogram fields of VC_HBITS bits), so a band costs at most
-// one atomic per (column, plane), per histogram bucket and per row of the chunk, zeros skipped.  All results are
-// integer sums and maxima: they do not depend on scheduling.
-// VC_BAND = 256: 65,536 x 65,536 views in chunks of 4,096 columns make 256 x 16 = 4,096 workgroups (16 per CU).
-constexpr uint32_t VC_BAND = 256;
-constexpr uint32_t VC_HBITS = 13;  // a thread counts at most VC_BAND x 16 = 2^12 views per band
-static_assert(VC_BAND * 16u < (1u << VC_HBITS), "packed histogram fields");
-// gs_view_census's device scratch (gs_handle::vc_buf): u64 accumulators, then the probes as {local column, version}
-enum VcSlot {
-    VC_OBS = 0, VC_VIEWS, VC_UNK, VC_BEHIND, VC_INEX, VC_MAXV, VC_MAXH,
-    VC_VH, VC_HH = VC_VH + GS_VC_BUCKETS, VC_REACH = VC_HH + GS_VC_BUCKETS, VC_NUM = VC_REACH + GS_VC_MAX_PROBES
-};
-struct VcArgs {
-    const uint8_t *up;         // nullptr: every row counts
-    uint32_t flags, n_probes;
-    unsigned long long *acc;   // [VC_NUM], zeroed
-    const uint32_t *probes;    // [n_probes][2] {local column or NONE, version}
-    uint32_t *owners, *rows;   // optional outputs, zeroed
-};
-__device__ __forceinline__ uint32_t wave_sum32(uint32_t x) {
-#pragma unroll
-    for (int dd = 32; dd >= 1; dd >>= 1) x += __shfl_xor(x, dd, WAVE);
-    return x;
-}
-__device__ __forceinline__ uint32_t wave_max32(uint32_t x) {
-#pragma unroll
-    for (int dd = 32; dd >= 1; dd >>= 1) x = max(x, (uint32_t)__shfl_xor(x, dd, WAVE));
-    return x;
-}
-// lag bucket (GS_VC_BUCKETS): 0 for lag 0, else min(19, bit length)
-__device__ __forceinline__ uint32_t vc_bucket(uint32_t lag) { return min(GS_VC_BUCKETS - 1u, 32u - (uint32_t)__clz(lag)); }
-// bit 7 of each byte -> the whole byte
-__device__ __forceinline__ uint32_t bytes7(uint32_t b7) { return (b7 >> 7) * 0xFFu; }
-// per-byte maximum of two words whose bytes are all < 2^7
-__device__ __forceinline__ uint32_t bmax7(uint32_t x, uint32_t y) {
-    const uint32_t ge = bytes7(((x | B7) - y) & B7);  // bytes where x >= y
-    return (x & ge) | (y & ~ge);
-}
-constexpr uint32_t VC_AHEAD = 3;  // rows in flight per thread: 16 waves per CU x 3 rows x 16 B per lane and region
-template <bool SWAR>
-__global__ __launch_bounds__(LB, 4) void k_view_census(Dev d, VcArgs a, uint32_t chunks) {
-    constexpr uint32_t PER = SWAR ? 16u : 8u;  // views per thread and row: one 16-byte load of the widest region
-    __shared__ uint32_t s_hist[2][GS_VC_BUCKETS];
-    __shared__ uint32_t s_rows[VC_BAND];
-    __shared__ uint32_t s_pi[GS_VC_MAX_PROBES];
-    __shared__ uint32_t s_pn;
-    // SWAR: an escaped column's own heartbeat mod 2^16 | slot << 16, per thread and column (read only for escaped
-    // columns, so it lives here and not in registers)
-    __shared__ uint32_t s_escpk[SWAR ? 16 : 1][LB];
-    const bool genm = !(d.flags & GS_CANONICAL);
-    const bool wantH = a.flags & GS_VC_HEARTBEATS;
-    const uint32_t tid = threadIdx.x;
-    const uint32_t rb = blockIdx.x / chunks, cb = blockIdx.x % chunks;
-    const uint32_t c_lo = cb * LB * PER, j0 = c_lo + tid * PER;
-    const uint32_t o0 = rb * VC_BAND, nrow = min(VC_BAND, d.N - o0);
-    const bool act = j0 < d.ncol;
-    const uint32_t nvt = act ? min(d.ncol - j0, PER) : 0u;  // this thread's real columns (padding is never counted)
-    for (uint32_t i = tid; i < 2u * GS_VC_BUCKETS; i += LB) (&s_hist[0][0])[i] = 0u;
-    for (uint32_t i = tid; i < VC_BAND; i += LB) s_rows[i] = 0u;
-    if (tid == 0) s_pn = 0u;
-    __syncthreads();
-    // the probes whose owner column lies in this chunk (none: the probes cost this workgroup nothing more)
-    if (tid < a.n_probes) {
-        const uint32_t c = a.probes[2u * tid];
-        if (c != NONE && c >= c_lo && c < c_lo + LB * PER) s_pi[atomicAdd(&s_pn, 1u)] = tid;
-    }
-    __syncthreads();
-    const uint32_t npc = s_pn;
-    uint32_t p_i = 0, p_c = 0, p_v = 0, p_M = 0, p_reach = 0;  // thread i < npc counts probe s_pi[i] over the band
-    if (tid < npc) {
-        p_i = s_pi[tid];
-        p_c = a.probes[2u * p_i];
-        p_v = a.probes[2u * p_i + 1u];
-        p_M = d.self_mv[p_c];
-    }
-    // the owners' own values and escape slots: the same for every row of the band
-    uint32_t own8v[4], owm7v[4], vm7v[4], esc7v[4];  // SWAR: four columns per word (k_hb_lag)
-    uint32_t ownR[SWAR ? 1 : 8], ownM[SWAR ? 1 : 8], slot[SWAR ? 1 : 8];  // per column
-    if constexpr (SWAR) {
-#pragma unroll
-        for (uint32_t q = 0; q < 4u; q++) {
-            const uint32_t jq = j0 + 4u * q;
-            own8v[q] = owm7v[q] = vm7v[q] = esc7v[q] = 0u;
-            if (jq >= d.ncol) continue;
-            const uint4 pk = *reinterpret_cast<const uint4 *>(d.self_pk + jq);
-            own8v[q] = (pk.x & 0xFFu) | ((pk.y & 0xFFu) << 8) | ((pk.z & 0xFFu) << 16) | (pk.w << 24);
-            owm7v[q] = ((pk.x >> 16) & 0x7Fu) | (((pk.y >> 16) & 0x7Fu) << 8) | (((pk.z >> 16) & 0x7Fu) << 16) |
-                       (((pk.w >> 16) & 0x7Fu) << 24);
-            const uint32_t nv = min(d.ncol - jq, 4u);
-            vm7v[q] = nv >= 4u ? B7 : B7 & ((1u << (8u * nv)) - 1u);  // bit 7 of the real columns
-            if (d.EC && wantH) {
-                uint32_t es[4], R[4];
-                ld4(d.esc_slot + jq, es);
-                ld4(d.self_hb + jq, R);
-#pragma unroll
-                for (uint32_t i = 0; i < 4; i++) {
-                    if (es[i] == NONE) continue;
-                    esc7v[q] |= 0x80u << (8u * i);
-                    s_escpk[4u * q + i][tid] = (R[i] & 0xFFFFu) | (es[i] << 16);  // (read back by this thread only)
-                }
-                esc7v[q] &= vm7v[q];
-            }
-        }
-    } else {
-#pragma unroll
-        for (uint32_t q = 0; q < 2u; q++) {
-            const uint32_t jq = j0 + 4u * q;
-            uint32_t R[4] = {0u, 0u, 0u, 0u}, M[4] = {0u, 0u, 0u, 0u}, es[4] = {NONE, NONE, NONE, NONE};
-            if (jq < d.ncol) {
-                ld4(d.self_hb + jq, R);
-                ld4(d.self_mv + jq, M);
-                if (d.EC) ld4(d.esc_slot + jq, es);
-            }
-#pragma unroll
-            for (uint32_t i = 0; i < 4; i++) { ownR[4u * q + i] = R[i]; ownM[4u * q + i] = M[i]; slot[4u * q + i] = es[i]; }
-        }
-    }
-    // one 16-byte load per region and row (8 bytes where this path's 8 views are bytes), VC_AHEAD rows ahead
-    v4u_t bh[VC_AHEAD], bm[VC_AHEAD];
-    auto ldv = [&](uint32_t o, v4u_t &nh, v4u_t &nm) {
-        nh = nm = v4u_t{0u, 0u, 0u, 0u};
-        if (!act) return;
-        const size_t p0 = pix(d, o, j0);
-        const uint8_t *m8 = reinterpret_cast<const uint8_t *>(d.mv), *h8 = reinterpret_cast<const uint8_t *>(d.hb);
-        if (SWAR) {
-            nm = __builtin_nontemporal_load(reinterpret_cast<const v4u_t *>(m8 + p0));
-            if (wantH) nh = __builtin_nontemporal_load(reinterpret_cast<const v4u_t *>(h8 + p0));
-            return;
-        }
-        if (d.mv8) {
-            const v2u_t x = __builtin_nontemporal_load(reinterpret_cast<const v2u_t *>(m8 + p0));
-            nm.x = x.x; nm.y = x.y;
-        } else {
-            nm = __builtin_nontemporal_load(reinterpret_cast<const v4u_t *>(d.mv + p0));
-        }
-        if (!wantH) return;
-        if (d.hb8) {
-            const v2u_t x = __builtin_nontemporal_load(reinterpret_cast<const v2u_t *>(h8 + p0));
-            nh.x = x.x; nh.y = x.y;
-        } else {
-            nh = __builtin_nontemporal_load(reinterpret_cast<const v4u_t *>(d.hb + p0));
-        }
-    };
-#pragma unroll
-    for (uint32_t u = 0; u < VC_AHEAD; u++) ldv(o0 + min(u, nrow - 1u), bh[u], bm[u]);
-    uint32_t t_views = 0, t_unk = 0, t_inex = 0, t_maxh = 0, n_obs = 0;
-    // per owner column, over the band.  SWAR: behind counts as bytes (widened to 16-bit pairs every 128 rows: beh[2 q]
-    // holds columns 4 q and 4 q + 2, beh[2 q + 1] columns 4 q + 1 and 4 q + 3), largest lags as bytes (mxv[q])
-    uint32_t beh[8], unk[SWAR ? 1 : 8], mxv[SWAR ? 4 : 8];
-    uint32_t beh8[4] = {0u, 0u, 0u, 0u};
-    // histogram fields of VC_HBITS bits: buckets 1-4 and 5-8 (SWAR: every lag < 2^8); the other path keeps buckets
-    // 1-4 here and sends the rare wider lags to the workgroup's LDS histogram
-    unsigned long long vlo = 0ull, vhi = 0ull, hlo = 0ull, hhi = 0ull;
-#pragma unroll
-    for (uint32_t k = 0; k < 8u; k++) beh[k] = 0u;
-#pragma unroll
-    for (uint32_t k = 0; k < (SWAR ? 4u : 8u); k++) mxv[k] = 0u;
-#pragma unroll
-    for (uint32_t k = 0; k < (SWAR ? 1u : 8u); k++) unk[k] = 0u;
-    auto hadd = [&](unsigned long long &lo, unsigned long long &hi, uint32_t pl, uint32_t lag) {
-        const uint32_t b = vc_bucket(lag) - 1u;  // lag != 0
-        const unsigned long long inc = 1ull << (VC_HBITS * (b & 3u));
-        if (b < 4u) lo += inc;
-        else if (SWAR && b < 8u) hi += inc;
-        else atomicAdd(&s_hist[pl][b + 1u], 1u);
-    };
-    // one row of the band: hr / mr = this thread's views of observer o
-    auto row = [&](uint32_t r, const v4u_t hr, const v4u_t mr) {
-        const uint32_t o = o0 + r;
-        const bool counted = !a.up || a.up[o];
-        if (counted) {
-            n_obs++;
-            uint32_t rowc = 0;  // this thread's columns the row is behind on or does not know
-            if (act) {
-                const uint32_t hw[4] = {hr.x, hr.y, hr.z, hr.w}, mw[4] = {mr.x, mr.y, mr.z, mr.w};
-                if constexpr (SWAR) {
-                    t_views += nvt;
-#pragma unroll
-                    for (uint32_t q = 0; q < 4u; q++) {
-                        const uint32_t vm7 = vm7v[q], vmask = bytes7(vm7);
-                        t_inex += (uint32_t)__popc(mw[q] & vm7);
-                        const uint32_t lagM = ((owm7v[q] | B7) - (mw[q] & L7)) & L7 & vmask;  // (own - view) mod 2^7
-                        if (lagM) {  // only non-zero lags go one view at a time (the histogram)
-                            const uint32_t nz = (lagM + L7) & B7;
-                            beh8[q] += nz >> 7;
-                            rowc += (uint32_t)__popc(nz);
-                            mxv[q] = bmax7(mxv[q], lagM);
-#pragma unroll
-                            for (uint32_t i = 0; i < 4; i++) {
-                                const uint32_t l = (lagM >> (8u * i)) & 0x7Fu;
-                                if (l) hadd(vlo, vhi, 0u, l);
-                            }
-                        }
-                        if (!wantH) continue;
-                        const uint32_t esc7 = esc7v[q];
-                        const uint32_t lagH = bsub(own8v[q], hw[q]) & vmask & ~bytes7(esc7);  // (own - view) mod 2^8
-                        if (lagH) {
-#pragma unroll
-                            for (uint32_t i = 0; i < 4; i++) {
-                                const uint32_t l = (lagH >> (8u * i)) & 0xFFu;
-                                if (!l) continue;
-                                t_maxh = max(t_maxh, l);
-                                hadd(hlo, hhi, 1u, l);
-                            }
-                        }
-                        if (esc7) {  // escaped columns: 16-bit views in GS_R_ESC16, one at a time
-#pragma unroll
-                            for (uint32_t i = 0; i < 4; i++) {
-                                if (!((esc7 >> (8u * i + 7u)) & 1u)) continue;
-                                const uint32_t pk = s_escpk[4u * q + i][tid];
-                                const uint32_t l = (pk - d.esc16[(size_t)o * d.EC + (pk >> 16)]) & 0xFFFFu;
-                                if (!l) continue;
-                                t_maxh = max(t_maxh, l);
-                                atomicAdd(&s_hist[1][vc_bucket(l)], 1u);
-                            }
-                        }
-                    }
-                } else {
-                    const size_t p0 = pix(d, o, j0);
-                    uint32_t ps[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
-                    if (genm) {
-                        const uint4 x = *reinterpret_cast<const uint4 *>(d.pos + p0), y = *reinterpret_cast<const uint4 *>(d.pos + p0 + 4);
-                        ps[0] = x.x; ps[1] = x.y; ps[2] = x.z; ps[3] = x.w; ps[4] = y.x; ps[5] = y.y; ps[6] = y.z; ps[7] = y.w;
-                    }
-#pragma unroll
-                    for (uint32_t k = 0; k < 8u; k++) {
-                        if (k >= nvt) continue;
-                        if (genm && ps[k] == NONE) {
-                            unk[SWAR ? 0 : k]++;
-                            t_unk++;
-                            rowc++;
-                            continue;
-                        }
-                        t_views++;
-                        const uint32_t w = d.mv8 ? mv_dec8((mw[k >> 2] >> (8u * (k & 3u))) & 0xFFu, ownM[SWAR ? 0 : k])
-                                                 : (mw[k >> 1] >> (16u * (k & 1u))) & 0xFFFFu;
-                        t_inex += w >> 15;
-                        const uint32_t l = ownM[SWAR ? 0 : k] - (w & MV_MASK);
-                        if (l) {
-                            beh[k]++;
-                            rowc++;
-                            mxv[SWAR ? 0 : k] = max(mxv[SWAR ? 0 : k], l);
-                            hadd(vlo, vhi, 0u, l);
-                        }
-                        if (!wantH) continue;
-                        uint32_t lh;
-                        const uint32_t R = ownR[SWAR ? 0 : k], sl = slot[SWAR ? 0 : k];
-                        if (sl != NONE) lh = (R - d.esc16[(size_t)o * d.EC + sl]) & 0xFFFFu;
-                        else if (d.hb8) lh = (R - ((hw[k >> 2] >> (8u * (k & 3u))) & 0xFFu)) & 0xFFu;
-                        else lh = (R - ((hw[k >> 1] >> (16u * (k & 1u))) & 0xFFFFu)) & 0xFFFFu;
-                        if (lh) {
-                            t_maxh = max(t_maxh, lh);
-                            hadd(hlo, hhi, 1u, lh);
-                        }
-                    }
-                }
-            }
-            if (a.rows && __ballot(rowc != 0u)) {  // one wave reduction; one global atomic per (row, chunk) below
-                const uint32_t s = wave_sum32(rowc);
-                if ((tid & 63u) == 0u && s) atomicAdd(&s_rows[r], s);
-            }
-            if (tid < npc) {
-                const size_t p = pix(d, o, p_c);
-                if (!genm || d.pos[p] != NONE) {
-                    const uint32_t w = d.mv8 ? mv_dec8(reinterpret_cast<const uint8_t *>(d.mv)[p], p_M) : (uint32_t)d.mv[p];
-                    p_reach += (w & MV_MASK) >= p_v;
-                }
-            }
-        }
-        if constexpr (SWAR) {
-            if ((r & 127u) == 127u || r + 1u == nrow) {  // byte counters hold 128 rows: widen to 16-bit pairs
-#pragma unroll
-                for (uint32_t q = 0; q < 4u; q++) {
-                    beh[2u * q] += beh8[q] & 0x00FF00FFu;
-                    beh[2u * q + 1u] += (beh8[q] >> 8) & 0x00FF00FFu;
-                    beh8[q] = 0u;
-                }
-            }
-        }
-    };
-    for (uint32_t r0 = 0; r0 < nrow; r0 += VC_AHEAD) {
-#pragma unroll
-        for (uint32_t u = 0; u < VC_AHEAD; u++) {
-            const uint32_t r = r0 + u;
-            if (r >= nrow) break;
-            const v4u_t hr = bh[u], mr = bm[u];
-            ldv(o0 + min(r + VC_AHEAD, nrow - 1u), bh[u], bm[u]);  // (past the band: the last row again, unused)
-            row(r, hr, mr);
-        }
-    }
-    // the band's results: at most one atomic per (column, plane), zeros skipped
-    uint32_t t_beh = 0, t_maxv = 0;
-#pragma unroll
-    for (uint32_t k = 0; k < PER; k++) {
-        uint32_t bk, mk, uk = 0u;
-        if constexpr (SWAR) {  // column k = 4 q + i: count in beh[2 q + (i & 1)], half i >> 1; lag in byte i of mxv[q]
-            bk = (beh[2u * (k >> 2) + (k & 1u)] >> (16u * ((k >> 1) & 1u))) & 0xFFFFu;
-            mk = (mxv[k >> 2] >> (8u * (k & 3u))) & 0xFFu;
-        } else {
-            bk = beh[k & 7u];
-            mk = mxv[SWAR ? 0 : (k & 7u)];
-            uk = unk[SWAR ? 0 : (k & 7u)];
-        }
-        t_beh += bk;
-        t_maxv = max(t_maxv, mk);
-        if (!a.owners || k >= nvt) continue;
-        if (bk) atomicAdd(&a.owners[j0 + k], bk);
-        if (uk) atomicAdd(&a.owners[d.ncol + j0 + k], uk);
-        if (mk) atomicMax(&a.owners[2u * d.ncol + j0 + k], mk);
-    }
-#pragma unroll
-    for (uint32_t b = 0; b < 4u; b++) {
-        const uint32_t m = (1u << VC_HBITS) - 1u, sh = VC_HBITS * b;
-        const uint32_t c0 = (uint32_t)(vlo >> sh) & m, c1 = (uint32_t)(vhi >> sh) & m;
-        const uint32_t c2 = (uint32_t)(hlo >> sh) & m, c3 = (uint32_t)(hhi >> sh) & m;
-        if (c0) atomicAdd(&s_hist[0][1u + b], c0);
-        if (c1) atomicAdd(&s_hist[0][5u + b], c1);
-        if (c2) atomicAdd(&s_hist[1][1u + b], c2);
-        if (c3) atomicAdd(&s_hist[1][5u + b], c3);
-    }
-    {
-        const uint32_t lane0 = (tid & 63u) == 0u;
-        const unsigned long long sv = wave_sum(t_views), su = wave_sum(t_unk), sb = wave_sum(t_beh), si = wave_sum(t_inex);
-        const uint32_t mv_ = wave_max32(t_maxv), mh_ = wave_max32(t_maxh);
-        if (lane0) {
-            if (sv) atomicAdd(&a.acc[VC_VIEWS], sv);
-            if (su) atomicAdd(&a.acc[VC_UNK], su);
-            if (sb) atomicAdd(&a.acc[VC_BEHIND], sb);
-            if (si) atomicAdd(&a.acc[VC_INEX], si);
-            if (mv_) atomicMax(&a.acc[VC_MAXV], (unsigned long long)mv_);
-            if (mh_) atomicMax(&a.acc[VC_MAXH], (unsigned long long)mh_);
-        }
-    }
-    if (cb == 0 && tid == 0 && n_obs) atomicAdd(&a.acc[VC_OBS], (unsigned long long)n_obs);
-    if (tid < npc && p_reach) atomicAdd(&a.acc[VC_REACH + p_i], (unsigned long long)p_reach);
-    __syncthreads();
-    for (uint32_t i = tid; i < 2u * GS_VC_BUCKETS; i += LB) {
-        const uint32_t c = (&s_hist[0][0])[i];
-        if (c) atomicAdd(&a.acc[VC_VH + i], (unsigned long long)c);
-    }
-    if (a.rows)
-        for (uint32_t i = tid; i < nrow; i += LB)
-            if (s_rows[i]) atomicAdd(&a.rows[o0 + i], s_rows[i]);
-}
-
-// Age census (gs_age_census): k_view_census's streaming pass over GS_R_MV, in ticks.  The caller's write log
-// wlog[ncol][WL] holds the tick at which each owner's max_version was first seen at each value (gs_note_writes); a
-// counted view at version v < M (M = the owner's own max_version) is behind, and its age is tick - wlog[j][v + 1],
-// the age of the oldest write its max_version does not cover (NONE there: counted in unlogged and nowhere else).
-// A pair the observer does not know (general layout) is a view at version 0.
-// The same workgroups as k_view_census: (band of VC_BAND rows, column chunk of LB x PER columns), one 16-byte
-// non-temporal load per thread and row, VC_AHEAD rows in flight, the owners' own versions loaded once.  In the
-// canonical 8-bit layout (SWAR) a row's 16 views are four words whose lags come out four at a time; a row with no
-// lag costs nothing more.  Only a view that is behind gathers its log entry: a row's gathers are issued together,
-// before any is used, and a chunk's log rows are shared by the whole band (and by the bands beside it), so they
-// come from L2.  Over the band a thread keeps, per column, the largest lag (= the smallest version seen, the
-// column's floor: one atomicMin per (band, column), none when it equals M), the age histogram as packed fields of
-// VC_HBITS bits, and the maxima; a row's largest age takes one wave reduction and one atomic per (row, chunk).
-// All results are integer sums, minima and maxima: they do not depend on scheduling.
-enum AcSlot {
-    AC_OBS = 0, AC_UNK, AC_BEHIND, AC_UNLOG, AC_MAXAGE, AC_SPREAD, AC_PENDING, AC_UNLOG_W, AC_MAXSPREAD, AC_MAXPEND,
-    AC_AH, AC_SH = AC_AH + GS_VC_BUCKETS, AC_PH = AC_SH + GS_VC_BUCKETS, AC_NUM = AC_PH + GS_VC_BUCKETS
-};
-struct AcArgs {
-    const uint8_t *up;         // nullptr: every row counts
-    const uint32_t *wlog;      // [ncol][WL]
-    uint32_t WL, tick;
-    unsigned long long *acc;   // [AC_NUM], zeroed
-    uint32_t *floor;           // [ncol], preset to the owners' own max_version
-    uint32_t *rows;            // optional, zeroed
-    uint32_t *done;            // optional, in/out (k_age_owners)
-};
-template <bool SWAR>
-__global__ __launch_bounds__(LB, 4) void k_age_census(Dev d, AcArgs a, uint32_t chunks) {
-    constexpr uint32_t PER = SWAR ? 16u : 8u;  // views per thread and row (k_view_census)
-    __shared__ uint32_t s_hist[GS_VC_BUCKETS];
-    __shared__ uint32_t s_rows[VC_BAND];
-    __shared__ uint32_t s_M[SWAR ? 16 : 1][LB];  // SWAR: the owners' full max_version, read only for views behind
-    const bool genm = !(d.flags & GS_CANONICAL);
-    const uint32_t tid = threadIdx.x;
-    const uint32_t rb = blockIdx.x / chunks, cb = blockIdx.x % chunks;
-    const uint32_t j0 = cb * LB * PER + tid * PER;
-    const uint32_t o0 = rb * VC_BAND, nrow = min(VC_BAND, d.N - o0);
-    const bool act = j0 < d.ncol;
-    const uint32_t nvt = act ? min(d.ncol - j0, PER) : 0u;  // this thread's real columns
-    for (uint32_t i = tid; i < GS_VC_BUCKETS; i += LB) s_hist[i] = 0u;
-    for (uint32_t i = tid; i < VC_BAND; i += LB) s_rows[i] = 0u;
-    uint32_t owm7v[4], vm7v[4];   // SWAR: four columns per word
-    uint32_t ownM[SWAR ? 1 : 8];  // per column
-#pragma unroll
-    for (uint32_t q = 0; q < PER / 4u; q++) {
-        const uint32_t jq = j0 + 4u * q;
-        uint32_t M[4] = {0u, 0u, 0u, 0u};
-        if (jq < d.ncol) ld4(d.self_mv + jq, M);
-        if constexpr (SWAR) {
-            owm7v[q] = (M[0] & 0x7Fu) | ((M[1] & 0x7Fu) << 8) | ((M[2] & 0x7Fu) << 16) | ((M[3] & 0x7Fu) << 24);
-            const uint32_t nv = jq < d.ncol ? min(d.ncol - jq, 4u) : 0u;
-            vm7v[q] = nv >= 4u ? B7 : B7 & ((1u << (8u * nv)) - 1u);  // bit 7 of the real columns
-#pragma unroll
-            for (uint32_t i = 0; i < 4; i++) s_M[4u * q + i][tid] = M[i];  // (read back by this thread only)
-        } else {
-#pragma unroll
-            for (uint32_t i = 0; i < 4; i++) ownM[4u * q + i] = M[i];
-        }
-    }
-    __syncthreads();
-    v4u_t bm[VC_AHEAD];
-    auto ldv = [&](uint32_t o, v4u_t &nm) {
-        nm = v4u_t{0u, 0u, 0u, 0u};
-        if (!act) return;
-        const size_t p0 = pix(d, o, j0);
-        const uint8_t *m8 = reinterpret_cast<const uint8_t *>(d.mv);
-        if (SWAR) {
-            nm = __builtin_nontemporal_load(reinterpret_cast<const v4u_t *>(m8 + p0));
-        } else if (d.mv8) {
-            const v2u_t x = __builtin_nontemporal_load(reinterpret_cast<const v2u_t *>(m8 + p0));
-            nm.x = x.x; nm.y = x.y;
-        } else {
-            nm = __builtin_nontemporal_load(reinterpret_cast<const v4u_t *>(d.mv + p0));
-        }
-    };
-#pragma unroll
-    for (uint32_t u = 0; u < VC_AHEAD; u++) ldv(o0 + min(u, nrow - 1u), bm[u]);
-    uint32_t t_unk = 0, t_beh = 0, t_unlog = 0, t_maxage = 0, n_obs = 0;
-    uint32_t mxl[SWAR ? 4 : 8];  // the largest lag per column over the band (SWAR: as bytes)
-#pragma unroll
-    for (uint32_t k = 0; k < (SWAR ? 4u : 8u); k++) mxl[k] = 0u;
-    unsigned long long ah[5] = {0ull, 0ull, 0ull, 0ull, 0ull};  // bucket b: field b & 3 of ah[b >> 2]
-    // the views of one row that are behind, lag[k] != 0: gather their log entries together, then count them
-    auto ages = [&](const uint32_t (&lag)[PER], uint32_t &rowm) {
-        uint32_t e[PER];
-#pragma unroll
-        for (uint32_t k = 0; k < PER; k++) {
-            e[k] = NONE;
-            if (!lag[k]) continue;
-            uint32_t Mk;
-            if constexpr (SWAR) Mk = s_M[k][tid];
-            else Mk = ownM[k];
-            const uint32_t w = Mk - lag[k] + 1u;  // the oldest write the view lacks (1 <= w <= M)
-            if (w < a.WL) e[k] = a.wlog[(size_t)(j0 + k) * a.WL + w];
-        }
-#pragma unroll
-        for (uint32_t k = 0; k < PER; k++) {
-            if (!lag[k]) continue;
-            t_beh++;
-            if (e[k] == NONE) { t_unlog++; continue; }
-            const uint32_t age = a.tick - e[k];
-            rowm = max(rowm, age);
-            const uint32_t b = vc_bucket(age);
-            const unsigned long long inc = 1ull << (VC_HBITS * (b & 3u));
-#pragma unroll
-            for (uint32_t g = 0; g < 5u; g++) ah[g] += (b >> 2) == g ? inc : 0ull;
-        }
-    };
-    auto row = [&](uint32_t r, const v4u_t mr) {
-        const uint32_t o = o0 + r;
-        if (a.up && !a.up[o]) return;
-        n_obs++;
-        uint32_t rowm = 0;  // this thread's largest age in the row
-        if (act) {
-            const uint32_t mw[4] = {mr.x, mr.y, mr.z, mr.w};
-            uint32_t lag[PER];
-            if constexpr (SWAR) {
-                uint32_t lagM[4], any = 0u;
-#pragma unroll
-                for (uint32_t q = 0; q < 4u; q++) {
-                    lagM[q] = ((owm7v[q] | B7) - (mw[q] & L7)) & L7 & bytes7(vm7v[q]);  // (own - view) mod 2^7
-                    any |= lagM[q];
-                }
-                if (any) {
-#pragma unroll
-                    for (uint32_t q = 0; q < 4u; q++) {
-                        mxl[q] = bmax7(mxl[q], lagM[q]);
-#pragma unroll
-                        for (uint32_t i = 0; i < 4; i++) lag[4u * q + i] = (lagM[q] >> (8u * i)) & 0x7Fu;
-                    }
-                    ages(lag, rowm);
-                }
-            } else {
-                const size_t p0 = pix(d, o, j0);
-                uint32_t ps[8] = {0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u};
-                if (genm) {
-                    const uint4 x = *reinterpret_cast<const uint4 *>(d.pos + p0), y = *reinterpret_cast<const uint4 *>(d.pos + p0 + 4);
-                    ps[0] = x.x; ps[1] = x.y; ps[2] = x.z; ps[3] = x.w; ps[4] = y.x; ps[5] = y.y; ps[6] = y.z; ps[7] = y.w;
-                }
-                uint32_t any = 0u;
-#pragma unroll
-                for (uint32_t k = 0; k < 8u; k++) {
-                    lag[k] = 0u;
-                    if (k >= nvt) continue;
-                    uint32_t v = 0u;  // a pair the observer does not know: a view at version 0
-                    if (genm && ps[k] == NONE) {
-                        t_unk++;
-                    } else {
-                        const uint32_t w = d.mv8 ? mv_dec8((mw[k >> 2] >> (8u * (k & 3u))) & 0xFFu, ownM[SWAR ? 0 : k])
-                                                 : (mw[k >> 1] >> (16u * (k & 1u))) & 0xFFFFu;
-                        v = w & MV_MASK;
-                    }
-                    lag[k] = ownM[SWAR ? 0 : k] - v;
-                    mxl[SWAR ? 0 : k] = max(mxl[SWAR ? 0 : k], lag[k]);
-                    any |= lag[k];
-                }
-                if (any) ages(lag, rowm);
-            }
-        }
-        t_maxage = max(t_maxage, rowm);
-        if (a.rows && __ballot(rowm != 0u)) {  // one wave reduction; one global atomic per (row, chunk) below
-            const uint32_t m = wave_max32(rowm);
-            if ((tid & 63u) == 0u) atomicMax(&s_rows[r], m);
-        }
-    };
-    for (uint32_t r0 = 0; r0 < nrow; r0 += VC_AHEAD) {
-#pragma unroll
-        for (uint32_t u = 0; u < VC_AHEAD; u++) {
-            const uint32_t r = r0 + u;
-            if (r >= nrow) break;
-            const v4u_t mr = bm[u];
-            ldv(o0 + min(r + VC_AHEAD, nrow - 1u), bm[u]);  // (past the band: the last row again, unused)
-            row(r, mr);
-        }
-    }
-    // the band's results: at most one atomicMin per column, none where no counted view is behind
-#pragma unroll
-    for (uint32_t k = 0; k < PER; k++) {
-        if (k >= nvt) continue;
-        uint32_t lk, Mk;
-        if constexpr (SWAR) {
-            lk = (mxl[k >> 2] >> (8u * (k & 3u))) & 0x7Fu;
-            Mk = s_M[k][tid];
-        } else {
-            lk = mxl[SWAR ? 0 : k];
-            Mk = ownM[SWAR ? 0 : k];
-        }
-        if (lk) atomicMin(&a.floor[j0 + k], Mk - lk);
-    }
-#pragma unroll
-    for (uint32_t b = 0; b < GS_VC_BUCKETS; b++) {
-        const uint32_t c = (uint32_t)(ah[b >> 2] >> (VC_HBITS * (b & 3u))) & ((1u << VC_HBITS) - 1u);
-        if (c) atomicAdd(&s_hist[b], c);
-    }
-    {
-        const unsigned long long su = wave_sum(t_unk), sb = wave_sum(t_beh), sl = wave_sum(t_unlog);
-        const uint32_t ma = wave_max32(t_maxage);
-        if ((tid & 63u) == 0u) {
-            if (su) atomicAdd(&a.acc[AC_UNK], su);
-            if (sb) atomicAdd(&a.acc[AC_BEHIND], sb);
-            if (sl) atomicAdd(&a.acc[AC_UNLOG], sl);
-            if (ma) atomicMax(&a.acc[AC_MAXAGE], (unsigned long long)ma);
-        }
-    }
-    if (cb == 0 && tid == 0 && n_obs) atomicAdd(&a.acc[AC_OBS], (unsigned long long)n_obs);
-    __syncthreads();
-    for (uint32_t i = tid; i < GS_VC_BUCKETS; i += LB)
-        if (s_hist[i]) atomicAdd(&a.acc[AC_AH + i], (unsigned long long)s_hist[i]);
-    if (a.rows)
-        for (uint32_t i = tid; i < nrow; i += LB)
-            if (s_rows[i]) atomicMax(&a.rows[o0 + i], s_rows[i]);
-}
-
-// The owner pass of gs_age_census, one thread per owner column, after k_age_census (nothing with no counted observer).
-// f = the column's floor, d0 = done[j] (f without done): the versions in (d0, f] have now reached every counted observer
-// (credited once: done[j] = max(d0, f)); those in (max(d0, f), M] are not yet everywhere.
-__global__ __launch_bounds__(LB) void k_age_owners(Dev d, AcArgs a) {
-    __shared__ uint32_t s_h[2][GS_VC_BUCKETS];
-    __shared__ uint32_t s_mx[2];
-    for (uint32_t i = threadIdx.x; i < 2u * GS_VC_BUCKETS; i += LB) (&s_h[0][0])[i] = 0u;
-    if (threadIdx.x < 2u) s_mx[threadIdx.x] = 0u;
-    __syncthreads();
-    const uint32_t j = blockIdx.x * LB + threadIdx.x;
-    uint32_t n_spread = 0, n_pend = 0, n_unlog = 0;
-    if (j < d.ncol && a.acc[AC_OBS]) {
-        const uint32_t *wl = a.wlog + (size_t)j * a.WL;
-        const uint32_t M = min(d.self_mv[j], a.WL - 1u), f = min(a.floor[j], M);
-        const uint32_t d0 = a.done ? a.done[j] : f, top = max(d0, f);
-        for (uint32_t w = d0 + 1u; w <= f; w++) {  // (runs only with done)
-            const uint32_t e = wl[w];
-            if (e == NONE) { n_unlog++; continue; }
-            n_spread++;
-            atomicAdd(&s_h[0][vc_bucket(a.tick - e)], 1u);
-            atomicMax(&s_mx[0], a.tick - e);
-        }
-        if (a.done && f > d0) a.done[j] = f;
-        for (uint32_t w = top + 1u; w <= M; w++) {
-            const uint32_t e = wl[w];
-            if (e == NONE) { n_unlog++; continue; }
-            n_pend++;
-            atomicAdd(&s_h[1][vc_bucket(a.tick - e)], 1u);
-            atomicMax(&s_mx[1], a.tick - e);
-        }
-    }
-    const unsigned long long ss = wave_sum(n_spread), sp = wave_sum(n_pend), su = wave_sum(n_unlog);
-    if ((threadIdx.x & 63u) == 0u) {
-        if (ss) atomicAdd(&a.acc[AC_SPREAD], ss);
-        if (sp) atomicAdd(&a.acc[AC_PENDING], sp);
-        if (su) atomicAdd(&a.acc[AC_UNLOG_W], su);
-    }
-    __syncthreads();
-    for (uint32_t i = threadIdx.x; i < 2u * GS_VC_BUCKETS; i += LB) {
-        const uint32_t c = (&s_h[0][0])[i];
-        if (c) atomicAdd(&a.acc[AC_SH + i], (unsigned long long)c);
-    }
-    if (threadIdx.x < 2u && s_mx[threadIdx.x]) atomicMax(&a.acc[AC_MAXSPREAD + threadIdx.x], (unsigned long long)s_mx[threadIdx.x]);
-}
-
-// gs_note_writes: the tick at which each owner's max_version was first seen at its current value
-__global__ __launch_bounds__(LB) void k_note_writes(Dev d, uint32_t *wlog, uint32_t WL, uint32_t tick) {
-    const uint32_t j = blockIdx.x * LB + threadIdx.x;
-    if (j >= d.ncol) return;
-    const uint32_t v = d.self_mv[j];
-    if (!v || v >= WL) return;
-    uint32_t *e = wlog + (size_t)j * WL + v;
-    if (*e == NONE) *e = tick;
-}
-
-// Detection census (gs_detect_census): a read-only streaming pass over GS_R_FD_STATE -- and, with thresholds (PHI),
-// over GS_R_FD_LAST and GS_R_FD -- that counts, over the pairs (observer o up, target j != o), the live / dead /
-// unknown pairs by whether the target is up, the detection latencies (time of death - down_since), the ages of
-// the undetected failures and of the false suspicions, and the pairs whose phi exceeds each swept threshold.
-// k_view_census's access pattern: one workgroup per (band of DC_BAND observer rows, chunk of LB x 16 columns), one
-// 16-byte non-temporal load of the state bytes per thread and row, rows in flight ahead of the one being reduced;
-// rows that are not counted are neither loaded nor reduced (a wave-uniform choice).  The rows counted are those of
-// DcArgs.obs, the targets' truth is DcArgs.up: gs_detect_census passes one array for both, gs_detect_census_for two
-// (an observer set that is one side of a partition, against what that side can reach).  The chunk's up bytes become two
-// byte masks per word (held in registers), down_since lives in LDS.
-// State only: four pairs per 32-bit word -- live and dead bytes by two bit operations, masked by the targets'
-// validity, accumulated in byte counters (widened every 128 rows).  The totals and the undetected ages follow from
-// the per-column counts at the end of the band (the age depends on the column alone).  Dead pairs go one at a time:
-// their time of death is loaded, bucketed into the workgroup's LDS histogram and folded into the column's
-// smallest / largest time of death.
-// PHI: per pair with a window, phi first in binary32 and division-free (numerator against threshold x denominator);
-// a value clear of every threshold by 2^-10 relative (the binary32 error is below 2^-20) counts for all or none of
-// them, any other is recomputed with k_phi_row's binary64
-// expression and compared with each threshold.  All results are integer sums, minima and maxima.
-constexpr uint32_t DC_BAND = 256;
-enum DcSlot {
-    DC_OBS = 0, DC_UP_PAIRS, DC_UP_LIVE, DC_UP_DEAD, DC_DN_PAIRS, DC_DN_LIVE, DC_DN_DEAD, DC_UP_WIN, DC_DN_WIN,
-    DC_UP_PHI, DC_DN_PHI, DC_OLD, DC_EARLY, DC_MAX /* latency, undetected age, false age */, DC_HIST = DC_MAX + 3,
-    DC_OVER = DC_HIST + 3 * GS_DC_BUCKETS, DC_NUM = DC_OVER + 2 * GS_DC_MAX_THRESHOLDS
-};
-struct DcArgs {
-    const uint8_t *obs;          // the rows counted (gs_detect_census: obs == up)
-    const uint8_t *up;           // the targets' truth
-    const uint32_t *down_since;  // nullptr: no latency / undetected-age histograms
-    uint32_t tick, tdec;         // tdec = the handle's latest tick: GS_R_FD_LAST decodes exactly against it
-    uint32_t n_thr;
-    float lo_all, hi_all;        // binary32 phi below lo_all: over no threshold; above hi_all: over every one
-    double thr[GS_DC_MAX_THRESHOLDS];
-    unsigned long long *acc;     // [DC_NUM], zeroed
-    uint32_t *targets, *rows;    // optional outputs: planes 0, 1, 3 zeroed, plane 2 GS_NONE; rows zeroed
-};
-__device__ __forceinline__ uint32_t dc_bucket(uint32_t x) { return min(GS_DC_BUCKETS - 1u, 32u - (uint32_t)__clz(x)); }
-// PHI holds 28 registers per row in flight: it is compiled for 2 workgroups per SIMD set (8 waves per CU x 2 rows x
-// 112 B per lane in flight), the state-only pass for 4 as k_view_census
-template <bool PHI>
-__global__ __launch_bounds__(LB, PHI ? 2 : 4) void k_detect_census(Dev d, DcArgs a, uint32_t chunks) {
-    constexpr uint32_t AHEAD = PHI ? 2u : 3u;  // rows in flight per thread (PHI: 112 B per row and lane)
-    __shared__ uint32_t s_hist[3][GS_DC_BUCKETS];
-    __shared__ uint32_t s_over[2][GS_DC_MAX_THRESHOLDS];
-    __shared__ uint32_t s_rows[DC_BAND];  // up targets held dead | down targets held live << 16
-    __shared__ uint32_t s_ds[16][LB];     // down_since of this thread's columns (read back by this thread only)
-    __shared__ double s_thr[GS_DC_MAX_THRESHOLDS];  // read on the binary64 path only
-    __shared__ uint32_t s_list[DC_BAND];  // the band's counted rows (up[o] != 0), in order: the loop runs over these
-    __shared__ uint32_t s_wc[LB / WAVE];
-    static_assert(DC_BAND == LB, "one thread per row of the band lists the counted rows");
-    const uint32_t tid = threadIdx.x;
-    const uint32_t rb = blockIdx.x / chunks, cb = blockIdx.x % chunks;
-    const uint32_t j0 = (cb * LB + tid) * 16u;
-    if (PHI && tid < GS_DC_MAX_THRESHOLDS) s_thr[tid] = a.thr[tid];
-    const uint32_t o0 = rb * DC_BAND, nrow = min(DC_BAND, d.N - o0);
-    const bool act = j0 < d.ncol;
-    const uint32_t nvt = act ? min(d.ncol - j0, 16u) : 0u;  // this thread's real columns (padding is never counted)
-    for (uint32_t i = tid; i < 3u * GS_DC_BUCKETS; i += LB) (&s_hist[0][0])[i] = 0u;
-    for (uint32_t i = tid; i < 2u * GS_DC_MAX_THRESHOLDS; i += LB) (&s_over[0][0])[i] = 0u;
-    s_rows[tid] = 0u;
-    // rows of down observers are neither loaded nor reduced: every load of the loop below is unconditional, so the
-    // compiler's wait for a row leaves the later rows in flight
-    const bool cnt_row = tid < nrow && a.obs[o0 + tid];
-    const unsigned long long cnt_b = __ballot(cnt_row);
-    if ((tid & 63u) == 0u) s_wc[tid >> 6] = (uint32_t)__popcll(cnt_b);
-    // the targets' truth: byte masks of the up and the down columns, four columns per word
-    uint32_t upm[4] = {0u, 0u, 0u, 0u}, dnm[4] = {0u, 0u, 0u, 0u};
-    uint32_t upcnt = 0, dncnt = 0;
-#pragma unroll
-    for (uint32_t k = 0; k < 16u; k++) {
-        uint32_t ds = 0u;
-        if (k < nvt) {
-            const uint32_t j = d.col_lo + j0 + k;
-            if (a.up[j]) {
-                upm[k >> 2] |= 1u << (8u * (k & 3u));
-                upcnt++;
-            } else {
-                dnm[k >> 2] |= 1u << (8u * (k & 3u));
-                dncnt++;
-                if (a.down_since) ds = a.down_since[j];
-            }
-        }
-        s_ds[k][tid] = ds;
-    }
-    __syncthreads();
-    uint32_t nlist = 0;
-    {
-        uint32_t base = 0;
-#pragma unroll
-        for (uint32_t w = 0; w < LB / WAVE; w++) {
-            if (w < (tid >> 6)) base += s_wc[w];
-            nlist += s_wc[w];
-        }
-        if (cnt_row) s_list[base + (uint32_t)__popcll(cnt_b & ((1ull << (tid & 63u)) - 1ull))] = tid;
-    }
-    __syncthreads();
-    nlist = __builtin_amdgcn_readfirstlane(nlist);
-    const uint32_t jc = act ? j0 : 0u;  // a thread past the last column loads column 0's bytes: its masks are empty
-    struct Row {
-        v4u_t s;
-        v4u_t l[PHI ? 2 : 1], f[PHI ? 4 : 1];
-    };
-    Row buf[AHEAD];
-    auto row_of = [&](uint32_t i) { return o0 + (uint32_t)__builtin_amdgcn_readfirstlane(s_list[i]); };
-    auto ldv = [&](uint32_t i, Row &r) {
-        const size_t p0 = pix(d, row_of(i), jc);
-        r.s = __builtin_nontemporal_load(reinterpret_cast<const v4u_t *>(d.fd_state + p0));
-        if constexpr (PHI) {
-#pragma unroll
-            for (uint32_t i = 0; i < 2u; i++)
-                r.l[i] = __builtin_nontemporal_load(reinterpret_cast<const v4u_t *>(d.fd_last + p0) + i);
-#pragma unroll
-            for (uint32_t i = 0; i < 4u; i++)
-                r.f[i] = __builtin_nontemporal_load(reinterpret_cast<const v4u_t *>(d.fd + p0) + i);
-        }
-    };
-#pragma unroll
-    for (uint32_t u = 0; u < AHEAD; u++)
-        if (nlist) ldv(min(u, nlist - 1u), buf[u]);
-    // per target column over the band: live / dead counts as bytes (widened to 16-bit pairs every 128 rows, as
-    // k_view_census's beh), smallest and largest time of death
-    uint32_t lv8[4] = {0u, 0u, 0u, 0u}, dd8[4] = {0u, 0u, 0u, 0u}, lv16[8], dd16[8], tmin[16], tmax[16];
-#pragma unroll
-    for (uint32_t k = 0; k < 8u; k++) lv16[k] = dd16[k] = 0u;
-#pragma unroll
-    for (uint32_t k = 0; k < 16u; k++) { tmin[k] = NONE; tmax[k] = 0u; }
-    const uint32_t n_obs = nlist;
-    uint32_t n_diag = 0, n_diag_dn = 0, t_early = 0, t_maxlat = 0, t_maxfalse = 0;
-    uint32_t t_upwin = 0, t_dnwin = 0, t_upphi = 0, t_dnphi = 0, t_old = 0, t_upall = 0, t_dnall = 0;
-    const uint32_t sum_mask = (1u << d.sum_bits) - 1u;
-    auto row = [&](uint32_t r, const Row &rw) {
-        const uint32_t o = row_of(r);
-        {
-            uint32_t rowc = 0;
-            if (act) {
-                uint32_t sw[4] = {rw.s.x, rw.s.y, rw.s.z, rw.s.w};
-                const uint32_t dj = o - (d.col_lo + j0);  // the diagonal pair is not counted (wraps when o is below)
-                if (dj < nvt) {
-                    n_diag++;
-#pragma unroll
-                    for (uint32_t q = 0; q < 4u; q++)
-                        if ((dj >> 2) == q) {  // (obs != up: a counted observer may itself be a down target)
-                            sw[q] &= ~(0xFFu << (8u * (dj & 3u)));
-                            n_diag_dn += (dnm[q] >> (8u * (dj & 3u))) & 1u;
-                        }
-                }
-#pragma unroll
-                for (uint32_t q = 0; q < 4u; q++) {
-                    const uint32_t x = sw[q], vm = upm[q] | dnm[q];
-                    const uint32_t lv = x & ~(x >> 1) & vm, dd = (x >> 1) & ~x & vm;
-                    lv8[q] += lv;
-                    dd8[q] += dd;
-                    rowc += (uint32_t)__popc(dd & upm[q]) | ((uint32_t)__popc(lv & dnm[q]) << 16);
-                    if (dd) {  // dead pairs, one at a time: the time of death
-#pragma unroll
-                        for (uint32_t i = 0; i < 4u; i++) {
-                            if (!((dd >> (8u * i)) & 1u)) continue;
-                            const uint32_t k = 4u * q + i;
-                            const uint32_t tod = d.tod[pix(d, o, j0 + k)];
-                            tmin[k] = min(tmin[k], tod);
-                            tmax[k] = max(tmax[k], tod);
-                            if ((upm[q] >> (8u * i)) & 1u) {  // a false suspicion: how long it has lasted
-                                const uint32_t age = a.tick - tod;
-                                t_maxfalse = max(t_maxfalse, age);
-                                atomicAdd(&s_hist[2][dc_bucket(age)], 1u);
-                            } else if (a.down_since) {
-                                const uint32_t ds = s_ds[k][tid];
-                                if (tod >= ds) {
-                                    t_maxlat = max(t_maxlat, tod - ds);
-                                    atomicAdd(&s_hist[0][dc_bucket(tod - ds)], 1u);
-                                } else {
-                                    t_early++;
-                                }
-                            }
-                        }
-                    }
-                }
-                if constexpr (PHI) {
-                    const uint32_t lw[8] = {rw.l[0].x, rw.l[0].y, rw.l[0].z, rw.l[0].w, rw.l[1].x, rw.l[1].y, rw.l[1].z, rw.l[1].w};
-                    const uint32_t fw[16] = {rw.f[0].x, rw.f[0].y, rw.f[0].z, rw.f[0].w, rw.f[1].x, rw.f[1].y, rw.f[1].z, rw.f[1].w,
-                                             rw.f[2].x, rw.f[2].y, rw.f[2].z, rw.f[2].w, rw.f[3].x, rw.f[3].y, rw.f[3].z, rw.f[3].w};
-#pragma unroll
-                    for (uint32_t k = 0; k < 16u; k++) {
-                        const uint32_t q = k >> 2, sh = 8u * (k & 3u);
-                        const uint32_t st = (sw[q] >> sh) & 0xFFu;
-                        const bool isup = (upm[q] >> sh) & 1u;
-                        if (!(st & FD_WIN) || !(((upm[q] | dnm[q]) >> sh) & 1u)) continue;
-                        if (isup) t_upwin++; else t_dnwin++;
-                        const uint32_t sum = fw[k] & sum_mask, cnt = fw[k] >> d.sum_bits;
-                        const uint32_t len = min(cnt, d.W);
-                        if (!len) continue;  // phi is None
-                        if (isup) t_upphi++; else t_dnphi++;
-                        const uint32_t l16 = (lw[k >> 1] >> (16u * (k & 1u))) & 0xFFFFu;
-                        // the report's age at tick, through the handle's latest tick (exact there: fd_get); a window
-                        // 2^15 ticks old or more is old, and decodes as tick - 2^15
-                        uint32_t age = (a.tick - a.tdec) + ((a.tdec - l16) & 0xFFFFu);
-                        if ((st & FD_OLD) || age >= FD_OLD_AGE) {
-                            age = FD_OLD_AGE;
-                            t_old++;
-                        }
-                        // phi = age (len + 5) / (sum + 5 prior), all in ticks: compared without dividing
-                        const float num = (float)age * ((float)len + 5.0f), den = (float)sum + d.prior5t_f;
-                        if (num < a.lo_all * den) continue;
-                        if (num > a.hi_all * den) {
-                            if (isup) t_upall++; else t_dnall++;
-                            continue;
-                        }
-                        const double mean = ((double)sum * TICK_S + d.prior5) / ((double)len + 5.0);
-                        const double phi = ((double)age * TICK_S) / mean;
-                        for (uint32_t i = 0; i < a.n_thr; i++)
-                            if (phi > s_thr[i]) atomicAdd(&s_over[isup ? 0 : 1][i], 1u);
-                    }
-                }
-            }
-            if (a.rows && __ballot(rowc != 0u)) {  // one wave reduction; one global atomic per (row, chunk, plane) below
-                const uint32_t s = wave_sum32(rowc);
-                if ((tid & 63u) == 0u && s) atomicAdd(&s_rows[o - o0], s);
-            }
-        }
-        if ((r & 127u) == 127u || r + 1u == nlist) {  // byte counters hold 128 rows: widen to 16-bit pairs
-#pragma unroll
-            for (uint32_t q = 0; q < 4u; q++) {
-                lv16[2u * q] += lv8[q] & 0x00FF00FFu;
-                lv16[2u * q + 1u] += (lv8[q] >> 8) & 0x00FF00FFu;
-                dd16[2u * q] += dd8[q] & 0x00FF00FFu;
-                dd16[2u * q + 1u] += (dd8[q] >> 8) & 0x00FF00FFu;
-                lv8[q] = dd8[q] = 0u;
-            }
-        }
-    };
-    for (uint32_t r0 = 0; r0 < nlist; r0 += AHEAD) {
-#pragma unroll
-        for (uint32_t u = 0; u < AHEAD; u++) {
-            const uint32_t r = r0 + u;
-            if (r >= nlist) break;
-            const Row rw = buf[u];
-            ldv(min(r + AHEAD, nlist - 1u), buf[u]);  // (past the list: the last row again, unused)
-            row(r, rw);
-        }
-    }
-    // the band's results: at most one atomic per (column, plane), zeros skipped; the totals and the undetected
-    // ages (tick - down_since of the column) from the per-column counts
-    uint32_t t_ul = 0, t_ud = 0, t_dl = 0, t_dd = 0, t_maxund = 0;
-#pragma unroll
-    for (uint32_t k = 0; k < 16u; k++) {
-        // column k = 4 q + i: counts in word 2 q + (i & 1), half i >> 1
-        const uint32_t w = 2u * (k >> 2) + (k & 1u), sh = 16u * ((k >> 1) & 1u);
-        const uint32_t lk = (lv16[w] >> sh) & 0xFFFFu, dk = (dd16[w] >> sh) & 0xFFFFu;
-        if (k >= nvt) continue;
-        if ((upm[k >> 2] >> (8u * (k & 3u))) & 1u) {
-            t_ul += lk;
-            t_ud += dk;
-        } else {
-            t_dl += lk;
-            t_dd += dk;
-            if (lk && a.down_since) {
-                const uint32_t ds = s_ds[k][tid], age = a.tick >= ds ? a.tick - ds : 0u;
-                t_maxund = max(t_maxund, age);
-                atomicAdd(&s_hist[1][dc_bucket(age)], lk);
-            }
-        }
-        if (!a.targets) continue;
-        if (lk) atomicAdd(&a.targets[j0 + k], lk);
-        if (dk) {
-            atomicAdd(&a.targets[d.ncol + j0 + k], dk);
-            atomicMin(&a.targets[2u * d.ncol + j0 + k], tmin[k]);
-            atomicMax(&a.targets[3u * d.ncol + j0 + k], tmax[k]);
-        }
-    }
-    {
-        const uint32_t lane0 = (tid & 63u) == 0u;
-        const uint32_t up_pairs = n_obs * upcnt - (n_diag - n_diag_dn), dn_pairs = n_obs * dncnt - n_diag_dn;
-        const uint32_t v[12] = {up_pairs, t_ul, t_ud, dn_pairs, t_dl, t_dd, t_upwin, t_dnwin, t_upphi, t_dnphi, t_old, t_early};
-#pragma unroll
-        for (uint32_t i = 0; i < 12u; i++) {
-            if (!PHI && i >= 6u && i < 11u) continue;
-            const uint32_t s = wave_sum32(v[i]);
-            if (lane0 && s) atomicAdd(&a.acc[DC_UP_PAIRS + i], (unsigned long long)s);
-        }
-        const uint32_t m[3] = {wave_max32(t_maxlat), wave_max32(t_maxund), wave_max32(t_maxfalse)};
-#pragma unroll
-        for (uint32_t i = 0; i < 3u; i++)
-            if (lane0 && m[i]) atomicMax(&a.acc[DC_MAX + i], (unsigned long long)m[i]);
-        if constexpr (PHI) {  // the pairs above every threshold
-            const uint32_t su = wave_sum32(t_upall), sd = wave_sum32(t_dnall);
-            if (lane0)
-                for (uint32_t i = 0; i < a.n_thr; i++) {
-                    if (su) atomicAdd(&s_over[0][i], su);
-                    if (sd) atomicAdd(&s_over[1][i], sd);
-                }
-        }
-    }
-    if (cb == 0 && tid == 0 && n_obs) atomicAdd(&a.acc[DC_OBS], (unsigned long long)n_obs);
-    __syncthreads();
-    for (uint32_t i = tid; i < 3u * GS_DC_BUCKETS; i += LB) {
-        const uint32_t c = (&s_hist[0][0])[i];
-        if (c) atomicAdd(&a.acc[DC_HIST + i], (unsigned long long)c);
-    }
-    if (PHI)
-        for (uint32_t i = tid; i < 2u * GS_DC_MAX_THRESHOLDS; i += LB) {
-            const uint32_t c = (&s_over[0][0])[i];
-            if (c) atomicAdd(&a.acc[DC_OVER + i], (unsigned long long)c);
-        }
-    if (a.rows)
-        for (uint32_t i = tid; i < nrow; i += LB) {
-            const uint32_t c = s_rows[i];
-            if (c & 0xFFFFu) atomicAdd(&a.rows[o0 + i], c & 0xFFFFu);
-            if (c >> 16) atomicAdd(&a.rows[d.N + o0 + i], c >> 16);
-        }
-}
-// a target nobody holds dead has no largest time of death either (the plane was zeroed for atomicMax)
-__global__ __launch_bounds__(LB) void k_detect_fix(uint32_t *targets, uint32_t ncol) {
-    const uint32_t j = blockIdx.x * LB + threadIdx.x;
-    if (j < ncol && !targets[ncol + j]) targets[3u * ncol + j] = NONE;
-}
-
 // Escaped owner columns (gs_config.esc_cols), after a lag sweep: one workgroup decides the moves -- an escaped
 // column none of whose views is hot any more (every lag < HOT_HB) goes back to 8-bit views, a column the sweep
 // flagged (a view lagging by >= 2^7) takes a free slot (none free: counted in err_hb_lag) -- and marks every
@@ -6069,744 +4938,10 @@ __global__ __launch_bounds__(XB, (KW == 4 ? TC_WAVES : 1)) void k_traffic(Dev d,
     }
 }
 
-// ------------------------------------------------------------------ peer selection
-// select_nodes_for_gossip (server.py:656-717) for every up node from its failure detector's
-// live / dead sets and its known peers, as _gossip_multiple uses them at round start
-// (server.py:442-469): F distinct peers sampled uniformly from the live set (from all known
-// peers while the live set is empty), one dead node with probability dead / (live + 1), and one
-// seed when no selected peer is a seed or live < seeds, with probability seeds / (live + dead)
-// (1 if both are empty; always when live = 0).  Random numbers: Philox4x32-10 keyed by the run
-// seed, counter (round, node, slot) -- reproducible, where the reference's Random() over set
-// iteration order is not.  Slots 0..F-1 feed Floyd's sample, SEL_DEAD and SEL_SEED
-// the two probes.  Restated on the CPU by oracle/peer_select.py.
-constexpr uint32_t SEL_DEAD = 14, SEL_SEED = 15;
-
-__host__ __device__ inline void philox4x32(uint32_t (&c)[4], uint32_t k0, uint32_t k1) {
-#pragma unroll
-    for (int i = 0; i < 10; i++) {
-        const uint64_t p0 = (uint64_t)0xD2511F53u * c[0], p1 = (uint64_t)0xCD9E8D57u * c[2];
-        const uint32_t hi0 = (uint32_t)(p0 >> 32), lo0 = (uint32_t)p0, hi1 = (uint32_t)(p1 >> 32), lo1 = (uint32_t)p1;
-        c[0] = hi1 ^ c[1] ^ k0;
-        c[1] = lo1;
-        c[2] = hi0 ^ c[3] ^ k1;
-        c[3] = lo0;
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-}
-__host__ __device__ inline void sel_rand(uint64_t seed, uint32_t round, uint32_t node, uint32_t slot, uint32_t (&c)[4]) {
-    c[0] = round; c[1] = node; c[2] = slot; c[3] = 0u;
-    philox4x32(c, (uint32_t)seed, (uint32_t)(seed >> 32));
-}
-__host__ __device__ inline uint32_t below(uint32_t x, uint32_t n) { return (uint32_t)(((uint64_t)x * n) >> 32); }
-__host__ __device__ inline double unit53(uint32_t a, uint32_t b) {
-    return (double)(((uint64_t)a << 21) ^ (uint64_t)(b >> 11)) * (1.0 / 9007199254740992.0);
-}
-
-// gs_draw_cuts: independent message loss, one thread per exchange.  Message m of the exchange is lost iff word m
-// of Philox(key = seed, counter = (round, initiator, responder, phase)) is below loss_q32; legs = the messages
-// delivered before the first lost one.  Restated on the CPU by aiocluster_amd/cuts.py.
-__global__ __launch_bounds__(LB) void k_draw_cuts(const int32_t *ini, const int32_t *res, uint32_t n, uint64_t seed,
-                                                  uint32_t round, uint32_t phase, uint32_t loss_q32, uint8_t *legs) {
-    const uint32_t e = blockIdx.x * LB + threadIdx.x;
-    if (e >= n) return;
-    uint32_t c[4] = {round, (uint32_t)ini[e], (uint32_t)res[e], phase};
-    philox4x32(c, (uint32_t)seed, (uint32_t)(seed >> 32));
-    legs[e] = c[0] < loss_q32 ? 0u : c[1] < loss_q32 ? 1u : c[2] < loss_q32 ? 2u : 3u;
-}
-
-// Zoned links (gs_draw_cuts_zoned, gs_filter_targets_zoned): link[x * Z + y] = the loss threshold of a message from a
-// node of zone x to a node of zone y, GS_LINK_DOWN = the link carries nothing.  The matrix travels as a kernel
-// argument (1 KiB) and is staged in LDS, where every lane looks up its own two entries.
-struct ZoneLinks {
-    uint32_t q[GS_MAX_ZONES * GS_MAX_ZONES];
-};
-static_assert(LB >= (int)(GS_MAX_ZONES * GS_MAX_ZONES), "one thread per link entry stages the matrix");
-// the two thresholds of the pair a -> b (forward: Syn and Ack, backward: SynAck); false = the connect fails: an index
-// or a zone byte out of range, or either direction down (asyncio.wait_for(open_coro), server.py:403-405, 424-431)
-__device__ __forceinline__ bool zone_pair(const uint32_t *s_link, const uint8_t *zone, uint32_t N, uint32_t Z,
-                                          uint32_t a, uint32_t b, uint32_t &fwd, uint32_t &bwd) {
-    if (a >= N || b >= N) return false;
-    const uint32_t za = zone[a], zb = zone[b];
-    if (za >= Z || zb >= Z) return false;
-    fwd = s_link[za * Z + zb];
-    bwd = s_link[zb * Z + za];
-    return fwd != GS_LINK_DOWN && bwd != GS_LINK_DOWN;
-}
-// gs_draw_cuts_zoned: k_draw_cuts with the threshold of each message's direction; a pair whose connect fails gets
-// GS_LEGS_NO_CONNECT.  Restated on the CPU by aiocluster_amd/cuts.py (draw_cuts_zoned).
-__global__ __launch_bounds__(LB) void k_draw_cuts_zoned(const int32_t *ini, const int32_t *res, uint32_t n, uint32_t N,
-                                                        uint64_t seed, uint32_t round, uint32_t phase,
-                                                        const uint8_t *zone, ZoneLinks lk, uint32_t Z, uint8_t *legs) {
-    __shared__ uint32_t s_link[GS_MAX_ZONES * GS_MAX_ZONES];
-    if (threadIdx.x < Z * Z) s_link[threadIdx.x] = lk.q[threadIdx.x];
-    __syncthreads();
-    const uint32_t e = blockIdx.x * LB + threadIdx.x;
-    if (e >= n) return;
-    const uint32_t a = (uint32_t)ini[e], b = (uint32_t)res[e];
-    uint32_t fwd = 0u, bwd = 0u;
-    if (!zone_pair(s_link, zone, N, Z, a, b, fwd, bwd)) {
-        legs[e] = (uint8_t)GS_LEGS_NO_CONNECT;
-        return;
-    }
-    uint32_t c[4] = {round, a, b, phase};
-    philox4x32(c, (uint32_t)seed, (uint32_t)(seed >> 32));
-    legs[e] = c[0] < fwd ? 0u : c[1] < bwd ? 1u : c[2] < fwd ? 2u : 3u;
-}
-// gs_filter_targets_zoned: the selected targets (gs_select_peers: out[o * per + slot], -1 = none) whose connect
-// would fail become -1; in may alias out (a thread reads and writes its own entry only).
-__global__ __launch_bounds__(LB) void k_zone_filter(const int32_t *in, int32_t *out, uint32_t n_targets, uint32_t per,
-                                                    uint32_t N, const uint8_t *zone, ZoneLinks lk, uint32_t Z,
-                                                    uint32_t *dropped) {
-    __shared__ uint32_t s_link[GS_MAX_ZONES * GS_MAX_ZONES];
-    if (threadIdx.x < Z * Z) s_link[threadIdx.x] = lk.q[threadIdx.x];
-    __syncthreads();
-    const uint32_t e = blockIdx.x * LB + threadIdx.x;
-    bool drop = false;
-    if (e < n_targets) {
-        const int32_t t = in[e];
-        uint32_t fwd, bwd;
-        drop = t >= 0 && !zone_pair(s_link, zone, N, Z, e / per, (uint32_t)t, fwd, bwd);
-        out[e] = drop ? -1 : t;
-    }
-    const unsigned long long m = __ballot(drop);
-    if (dropped && (threadIdx.x & 63) == 0 && m) atomicAdd(dropped, (uint32_t)__popcll(m));
-}
-
-// per row: live / dead / known-peer counts (observer up); SCNT[o] = {live, dead, peers, 0}
-__global__ __launch_bounds__(LB) void k_sel_count(Dev d, const uint8_t *up, uint32_t *scnt) {
-    const uint32_t o = blockIdx.x;
-    if (!up[o]) return;
-    const bool genm = !(d.flags & GS_CANONICAL);
-    uint32_t L = 0, D = 0, P = 0;
-    for (uint32_t j = threadIdx.x; j < d.ncol; j += LB) {
-        const size_t p = pix(d, o, j);
-        if (j == o || (genm && d.pos[p] == NONE)) continue;
-        const uint32_t st = d.fd_state[p] & FD_MEMB;
-        P++;
-        L += st == 1u;
-        D += st >= 2u;
-    }
-    __shared__ uint32_t s3[3][LB / WAVE];
-    const uint32_t w = threadIdx.x >> 6;
-    const unsigned long long l = wave_sum(L), dd = wave_sum(D), pp = wave_sum(P);
-    if ((threadIdx.x & 63) == 0) { s3[0][w] = (uint32_t)l; s3[1][w] = (uint32_t)dd; s3[2][w] = (uint32_t)pp; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint32_t a = 0, b = 0, c = 0;
-        for (int i = 0; i < LB / WAVE; i++) { a += s3[0][i]; b += s3[1][i]; c += s3[2][i]; }
-        scnt[o * 4 + 0] = a; scnt[o * 4 + 1] = b; scnt[o * 4 + 2] = c;
-    }
-}
-
-// The seed probe (server.py:700-717) of row o and the resolved picks out: thread 0 of the resolve kernels.
-__device__ void sel_seed_probe(const Dev &d, uint32_t o, uint32_t L, uint32_t D, uint32_t F, uint64_t seed,
-                               uint32_t round, const int32_t *seeds, uint32_t n_seeds, const uint32_t *s_hit,
-                               int32_t *oo, const uint32_t *pre = nullptr) {
-    bool has_seed = false;
-    uint32_t S = 0;
-    for (uint32_t q = 0; q < n_seeds; q++) {
-        if ((uint32_t)seeds[q] == o) continue;
-        S++;
-        for (uint32_t i = 0; i < F; i++) has_seed |= s_hit[i] == (uint32_t)seeds[q];
-    }
-    uint32_t pick = NONE;
-    if (S && (!has_seed || L < S)) {
-        uint32_t c[4];
-        if (pre) {  // (drawn earlier by another lane: the same counter, the same values)
-            for (int q = 0; q < 4; q++) c[q] = pre[q];
-        } else {
-            sel_rand(seed, round, o, SEL_SEED, c);
-        }
-        const double ps = (L + D) == 0u ? 1.0 : (double)S / (double)(L + D);
-        if (L == 0u || unit53(c[0], c[1]) <= ps) {
-            uint32_t k = below(c[2], S);
-            for (uint32_t q = 0; q < n_seeds; q++) {
-                if ((uint32_t)seeds[q] == o) continue;
-                if (k-- == 0) { pick = (uint32_t)seeds[q]; break; }
-            }
-        }
-    }
-    for (uint32_t i = 0; i < F + 1; i++) oo[i] = s_hit[i] == NONE ? -1 : (int32_t)(d.col_lo + s_hit[i]);
-    oo[F + 1] = pick == NONE ? -1 : (int32_t)pick;
-}
-
-// Canonical layout (every observer knows every owner, no dict positions): the same counts from 16 state
-// bytes per thread and load -- live = membership 1, dead = membership 2 (bit 1), known = every column but
-// the observer's own (whose state stays unknown: liveness skips it).
-__device__ __forceinline__ uint32_t memb_live4(uint32_t w) {  // bytes whose membership bits are 01
-    const uint32_t m = w & 0x03030303u;
-    return m & ~(m >> 1) & 0x01010101u;
-}
-__device__ __forceinline__ uint32_t memb_dead4(uint32_t w) { return (w >> 1) & 0x01010101u; }
-__global__ __launch_bounds__(LB) void k_sel_count16(Dev d, const uint8_t *up, uint32_t *scnt) {
-    const uint32_t o = blockIdx.x;
-    if (!up[o]) return;
-    uint32_t L = 0, D = 0;
-    const uint8_t *row = d.fd_state + (size_t)o * d.NP;
-    for (uint32_t j0 = threadIdx.x * 16u; j0 < d.ncol; j0 += LB * 16u) {
-        const uint4 v = *reinterpret_cast<const uint4 *>(row + j0);  // NP is a multiple of 64: in the row
-        const uint32_t w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-        for (int q = 0; q < 4; q++) {
-            const uint32_t jq = j0 + 4u * q;
-            uint32_t keep = 0x01010101u;  // columns < ncol (the padding's state bytes are never written: 0)
-            if (jq + 4u > d.ncol) keep = jq >= d.ncol ? 0u : (0x01010101u >> (8u * (jq + 4u - d.ncol)));
-            const uint32_t js = o - d.col_lo - jq;  // the observer's own column is not a peer
-            if (js < 4u) keep &= ~(0x01u << (8u * js));
-            L += (uint32_t)__popc(memb_live4(w[q]) & keep);
-            D += (uint32_t)__popc(memb_dead4(w[q]) & keep);
-        }
-    }
-    __shared__ uint32_t s2[2][LB / WAVE];
-    const uint32_t wv = threadIdx.x >> 6;
-    const unsigned long long l = wave_sum(L), dd = wave_sum(D);
-    if ((threadIdx.x & 63) == 0) { s2[0][wv] = (uint32_t)l; s2[1][wv] = (uint32_t)dd; }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        uint32_t a = 0, b = 0;
-        for (int i = 0; i < LB / WAVE; i++) { a += s2[0][i]; b += s2[1][i]; }
-        scnt[o * 4 + 0] = a;
-        scnt[o * 4 + 1] = b;
-        scnt[o * 4 + 2] = d.ncol - (o - d.col_lo < d.ncol ? 1u : 0u);  // known: every column but o's own
-    }
-}
-
-// Floyd's sample of k distinct ranks of [0, n) (n = L live, or P known when none is live) and the dead probe,
-// by rank, into so[0..F] (NONE where absent: so[] starts all NONE)
-// pre (optional): the draws of counters (round, o, slot) already made, pre[4 i + q] for slot i < F, then SEL_DEAD
-__device__ inline void sel_ranks(uint32_t o, uint32_t L, uint32_t D, uint32_t P, uint32_t F, uint64_t seed,
-                                 uint32_t round, uint32_t *so, const uint32_t *pre = nullptr) {
-    const uint32_t n = L ? L : P, k = F < n ? F : n;
-    uint32_t c[4];
-    for (uint32_t i = 0; i < k; i++) {
-        const uint32_t t = n - k + i;
-        if (pre) c[0] = pre[4 * i];
-        else sel_rand(seed, round, o, i, c);
-        uint32_t r = below(c[0], t + 1);
-        for (uint32_t q = 0; q < i; q++)
-            if (so[q] == r) { r = t; break; }
-        so[i] = r;
-    }
-    if (D) {
-        if (pre) {
-            for (int q = 0; q < 4; q++) c[q] = pre[4 * F + q];
-        } else {
-            sel_rand(seed, round, o, SEL_DEAD, c);
-        }
-        const double pd = (double)D / (double)(L + 1u);
-        if (pd > unit53(c[0], c[1])) so[F] = below(c[2], D);
-    }
-}
-// Floyd's sample of k distinct ranks of [0, n) and the dead probe, by rank; targets resolved next.
-// sel[o][0..F) = live (or peer) ranks, sel[o][F] = dead rank, NONE where absent.
-__global__ __launch_bounds__(LB) void k_sel_pick(Dev d, const uint8_t *up, const uint32_t *scnt, uint32_t F,
-                                                 uint64_t seed, uint32_t round, uint32_t *sel) {
-    const uint32_t o = blockIdx.x * LB + threadIdx.x;
-    if (o >= d.N) return;
-    uint32_t *so = sel + (size_t)o * (F + 2);
-    for (uint32_t i = 0; i < F + 2; i++) so[i] = NONE;
-    if (!up[o]) return;
-    sel_ranks(o, scnt[o * 4 + 0], scnt[o * 4 + 1], scnt[o * 4 + 2], F, seed, round, so);
-}
-
-// k-th set bit (k < popc(m)) of a 16-bit mask
-__device__ __forceinline__ uint32_t nth_bit16(uint32_t m, uint32_t k) {
-    for (uint32_t i = 0; i < k; i++) m &= m - 1u;
-    return (uint32_t)__builtin_ctz(m);
-}
-// Canonical layout: k_sel_resolve with 16 columns per thread and step (one 16-byte state load); the pool
-// (live, or every known node when none is live) and dead masks are ranked by a block scan of their
-// popcounts, so a row takes ncol / 4096 steps instead of ncol / 256.
-__global__ __launch_bounds__(LB) void k_sel_resolve16(Dev d, const uint8_t *up, const uint32_t *scnt, uint32_t F,
-                                                      uint64_t seed, uint32_t round, const int32_t *seeds,
-                                                      uint32_t n_seeds, const uint32_t *sel, int32_t *out) {
-    __shared__ uint32_t s_w[LB / WAVE][2];
-    __shared__ uint32_t s_rank[10], s_hit[10];
-    const uint32_t o = blockIdx.x;
-    int32_t *oo = out + (size_t)o * (F + 2);
-    if (!up[o]) {
-        for (uint32_t i = threadIdx.x; i < F + 2; i += LB) oo[i] = -1;
-        return;
-    }
-    const uint32_t L = scnt[o * 4 + 0];
-    const bool from_live = L != 0;
-    if (threadIdx.x < F + 1) {
-        s_rank[threadIdx.x] = sel[(size_t)o * (F + 2) + threadIdx.x];
-        s_hit[threadIdx.x] = NONE;
-    }
-    __syncthreads();
-    const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
-    const uint8_t *row = d.fd_state + (size_t)o * d.NP;
-    uint32_t base_pool = 0, base_dead = 0;
-    for (uint32_t b0 = 0; b0 < d.ncol; b0 += LB * 16u) {
-        const uint32_t j0 = b0 + threadIdx.x * 16u;
-        uint32_t mp = 0, md = 0;  // bit i: column j0 + i is in the pool / dead
-        if (j0 < d.ncol) {
-            const uint4 v = *reinterpret_cast<const uint4 *>(row + j0);
-            const uint32_t wd[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-            for (int q = 0; q < 4; q++) {
-#pragma unroll
-                for (int b = 0; b < 4; b++) {
-                    const uint32_t j = j0 + 4u * q + b;
-                    const uint32_t st = (wd[q] >> (8 * b)) & FD_MEMB;
-                    const bool valid = j < d.ncol && d.col_lo + j != o;
-                    const bool live = valid && st == 1u, dead = valid && st >= 2u;
-                    mp |= (uint32_t)(from_live ? live : valid) << (4 * q + b);
-                    md |= (uint32_t)dead << (4 * q + b);
-                }
-            }
-        }
-        const uint32_t cp = (uint32_t)__popc(mp), cd = (uint32_t)__popc(md);
-        const uint32_t ip = wave_incl_scan(cp), id = wave_incl_scan(cd);
-        if (lane == 63) { s_w[w][0] = ip; s_w[w][1] = id; }
-        __syncthreads();
-        uint32_t op = base_pool + ip - cp, od = base_dead + id - cd, tp = 0, td = 0;
-        for (uint32_t i = 0; i < LB / WAVE; i++) {
-            if (i < w) { op += s_w[i][0]; od += s_w[i][1]; }
-            tp += s_w[i][0];
-            td += s_w[i][1];
-        }
-        for (uint32_t i = 0; i < F; i++) {
-            const uint32_t r = s_rank[i];
-            if (r != NONE && r >= op && r < op + cp) s_hit[i] = j0 + nth_bit16(mp, r - op);
-        }
-        {
-            const uint32_t r = s_rank[F];
-            if (r != NONE && r >= od && r < od + cd) s_hit[F] = j0 + nth_bit16(md, r - od);
-        }
-        base_pool += tp;
-        base_dead += td;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) sel_seed_probe(d, o, L, scnt[o * 4 + 1], F, seed, round, seeds, n_seeds, s_hit, oo);
-}
-
-// Canonical layout, ncol <= SEL_ROW_IT * 4096: k_sel_count16 + k_sel_pick + k_sel_resolve16 in one workgroup per
-// row that reads the row's state bytes once -- each thread keeps its 16-column live / dead masks of every
-// 4,096-column step in registers: the counts, the ranks (thread 0), then one block scan of all steps at once
-// (one barrier instead of two per step)
-constexpr uint32_t SEL_ROW_IT = 16;
-__global__ __launch_bounds__(LB, 4) void k_sel_row16(Dev d, const uint8_t *up, uint32_t F, uint64_t seed, uint32_t round,
-                                                  const int32_t *seeds, uint32_t n_seeds, uint32_t *scnt, int32_t *out) {
-    // the live / dead masks of every step in LDS (16 KB: registers would hold the occupancy to 2 waves per SIMD)
-    __shared__ uint16_t s_m[SEL_ROW_IT][2][LB];
-    __shared__ uint32_t s_w[SEL_ROW_IT][LB / WAVE][2];
-    __shared__ uint32_t s_rank[10], s_hit[10], s_cnt[2], s_rnd[10 * 4];
-    const uint32_t o = blockIdx.x;
-    int32_t *oo = out + (size_t)o * (F + 2);
-    if (!up[o]) {
-        for (uint32_t i = threadIdx.x; i < F + 2; i += LB) oo[i] = -1;
-        return;
-    }
-    const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
-    if (threadIdx.x < F + 2) {  // the row's Philox draws, one lane each (thread 0 only does the arithmetic)
-        uint32_t c[4];
-        sel_rand(seed, round, o, threadIdx.x < F ? threadIdx.x : threadIdx.x == F ? SEL_DEAD : SEL_SEED, c);
-        for (int q = 0; q < 4; q++) s_rnd[4 * threadIdx.x + q] = c[q];
-    }
-    const uint8_t *row = d.fd_state + (size_t)o * d.NP;
-    const uint32_t nit = (d.ncol + LB * 16u - 1u) / (LB * 16u);
-    uint32_t L = 0, D = 0;
-#pragma unroll
-    for (uint32_t h = 0; h < SEL_ROW_IT; h += 8) {  // eight steps' loads in flight at a time
-        uint4 v[8];
-#pragma unroll
-        for (uint32_t u = 0; u < 8; u++) {
-            // unconditional (a clamped address, masked below): loads under a branch would be waited for one by one
-            const uint32_t j0 = (h + u) * LB * 16u + threadIdx.x * 16u;
-            v[u] = *reinterpret_cast<const uint4 *>(row + min(j0, d.NP - 16u));
-        }
-#pragma unroll
-        for (uint32_t u = 0; u < 8; u++) {
-            const uint32_t it = h + u, j0 = it * LB * 16u + threadIdx.x * 16u;
-            const bool inrow = it < nit && j0 < d.ncol;
-            const uint32_t wd[4] = {v[u].x, v[u].y, v[u].z, v[u].w};
-            uint32_t a = 0u, b = 0u;
-#pragma unroll
-            for (int q = 0; q < 4; q++) {
-                const uint32_t jq = j0 + 4u * q;
-                uint32_t keep = inrow ? 0x01010101u : 0u;  // (k_sel_count16's column mask: in range, not o's own)
-                if (jq + 4u > d.ncol) keep = jq >= d.ncol ? 0u : (keep >> (8u * (jq + 4u - d.ncol)));
-                const uint32_t js = o - d.col_lo - jq;
-                if (js < 4u) keep &= ~(0x01u << (8u * js));
-                // bit 0 of each byte -> 4 adjacent bits: bytes 0..3 times 2^21, 2^14, 2^7, 1 land on bits 21..24
-                a |= (((memb_live4(wd[q]) & keep) * 0x204081u) >> 21 & 0xFu) << (4 * q);
-                b |= (((memb_dead4(wd[q]) & keep) * 0x204081u) >> 21 & 0xFu) << (4 * q);
-            }
-            s_m[it][0][threadIdx.x] = (uint16_t)a;
-            s_m[it][1][threadIdx.x] = (uint16_t)b;
-            L += (uint32_t)__popc(a);
-            D += (uint32_t)__popc(b);
-        }
-    }
-    {
-        const unsigned long long l = wave_sum(L), dd = wave_sum(D);
-        if (lane == 0) { s_w[0][w][0] = (uint32_t)l; s_w[0][w][1] = (uint32_t)dd; }
-        __syncthreads();
-        if (threadIdx.x == 0) {
-            uint32_t a = 0, b = 0;
-            for (uint32_t i = 0; i < LB / WAVE; i++) { a += s_w[0][i][0]; b += s_w[0][i][1]; }
-            const uint32_t P = d.ncol - (o - d.col_lo < d.ncol ? 1u : 0u);  // known: every column but o's own
-            scnt[o * 4 + 0] = a;
-            scnt[o * 4 + 1] = b;
-            scnt[o * 4 + 2] = P;
-            s_cnt[0] = a;
-            s_cnt[1] = b;
-            uint32_t so[10];
-            for (uint32_t i = 0; i < F + 2; i++) so[i] = NONE;
-            sel_ranks(o, a, b, P, F, seed, round, so, s_rnd);
-            for (uint32_t i = 0; i < F + 1; i++) {
-                s_rank[i] = so[i];
-                s_hit[i] = NONE;
-            }
-        }
-        __syncthreads();
-    }
-    L = s_cnt[0];
-    const bool from_live = L != 0;
-    // the pool (live, or every known column when none is live) and dead ranks of every step, one block scan
-    auto pool = [&](uint32_t it) {
-        if (from_live) return (uint32_t)s_m[it][0][threadIdx.x];
-        const uint32_t j0 = it * LB * 16u + threadIdx.x * 16u;  // every valid column
-        uint32_t m = j0 >= d.ncol ? 0u : d.ncol - j0 >= 16u ? 0xFFFFu : (1u << (d.ncol - j0)) - 1u;
-        const uint32_t js = o - d.col_lo - j0;
-        if (js < 16u) m &= ~(1u << js);
-        return m;
-    };
-    uint32_t ex[SEL_ROW_IT];  // the wave-exclusive scans: pool | dead << 16 (each < 2^10)
-#pragma unroll
-    for (uint32_t it = 0; it < SEL_ROW_IT; it++) {
-        const uint32_t c2 = (uint32_t)__popc(pool(it)) | ((uint32_t)__popc((uint32_t)s_m[it][1][threadIdx.x]) << 16);
-        const uint32_t i2 = wave_scan_dpp(c2);  // (both halves at once: no carry out of the low one)
-        ex[it] = i2 - c2;
-        if (lane == 63) { s_w[it][w][0] = i2 & 0xFFFFu; s_w[it][w][1] = i2 >> 16; }
-    }
-    __syncthreads();
-    uint32_t bp = 0, bd = 0;  // ranks before this step
-#pragma unroll
-    for (uint32_t it = 0; it < SEL_ROW_IT; it++) {  // (unrolled: ex[] stays in registers)
-        uint32_t op = bp + (ex[it] & 0xFFFFu), od = bd + (ex[it] >> 16);
-#pragma unroll
-        for (uint32_t i = 0; i < LB / WAVE; i++) {
-            const uint32_t xp = s_w[it][i][0], xd = s_w[it][i][1];
-            if (i < w) { op += xp; od += xd; }
-            bp += xp;
-            bd += xd;
-        }
-        const uint32_t j0 = it * LB * 16u + threadIdx.x * 16u;
-        const uint32_t mp = pool(it), md = s_m[it][1][threadIdx.x];
-        const uint32_t cp = (uint32_t)__popc(mp), cd = (uint32_t)__popc(md);
-        if (cp) {
-            for (uint32_t i = 0; i < F; i++) {
-                const uint32_t r = s_rank[i];
-                if (r != NONE && r >= op && r < op + cp) s_hit[i] = j0 + nth_bit16(mp, r - op);
-            }
-        }
-        const uint32_t r = s_rank[F];
-        if (cd && r != NONE && r >= od && r < od + cd) s_hit[F] = j0 + nth_bit16(md, r - od);
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) sel_seed_probe(d, o, L, s_cnt[1], F, seed, round, seeds, n_seeds, s_hit, oo, s_rnd + 4 * (F + 1));
-}
-
-// Resolve ranks to node ids in column order (one workgroup per row), then the seed probe.
-// out[o][0..F) live picks, out[o][F] dead pick, out[o][F+1] seed pick (NONE = none).
-__global__ __launch_bounds__(LB) void k_sel_resolve(Dev d, const uint8_t *up, const uint32_t *scnt, uint32_t F,
-                                                    uint64_t seed, uint32_t round, const int32_t *seeds,
-                                                    uint32_t n_seeds, const uint32_t *sel, int32_t *out) {
-    __shared__ uint32_t s_w[LB / WAVE][2];
-    __shared__ uint32_t s_rank[10], s_hit[10];
-    const uint32_t o = blockIdx.x;
-    int32_t *oo = out + (size_t)o * (F + 2);
-    if (!up[o]) {
-        for (uint32_t i = threadIdx.x; i < F + 2; i += LB) oo[i] = -1;
-        return;
-    }
-    const bool genm = !(d.flags & GS_CANONICAL);
-    const uint32_t L = scnt[o * 4 + 0];
-    const bool from_live = L != 0;
-    if (threadIdx.x < F + 1) {
-        s_rank[threadIdx.x] = sel[(size_t)o * (F + 2) + threadIdx.x];
-        s_hit[threadIdx.x] = NONE;
-    }
-    __syncthreads();
-    const uint32_t lane = threadIdx.x & 63u, w = threadIdx.x >> 6;
-    uint32_t base_pool = 0, base_dead = 0;
-    for (uint32_t j0 = 0; j0 < d.ncol; j0 += LB) {
-        const uint32_t j = j0 + threadIdx.x;
-        bool known = false, live = false, dead = false;
-        if (j < d.ncol && j != o) {
-            const size_t p = pix(d, o, j);
-            known = !genm || d.pos[p] != NONE;
-            if (known) {
-                const uint32_t st = d.fd_state[p] & FD_MEMB;
-                live = st == 1u;
-                dead = st >= 2u;
-            }
-        }
-        const bool inpool = from_live ? live : known;
-        const unsigned long long mp = __ballot(inpool), md = __ballot(dead);
-        if (lane == 0) { s_w[w][0] = (uint32_t)__popcll(mp); s_w[w][1] = (uint32_t)__popcll(md); }
-        __syncthreads();
-        uint32_t op = base_pool, od = base_dead, tp = 0, td = 0;
-        for (uint32_t i = 0; i < LB / WAVE; i++) {
-            if (i < w) { op += s_w[i][0]; od += s_w[i][1]; }
-            tp += s_w[i][0];
-            td += s_w[i][1];
-        }
-        const uint64_t lm = (1ull << lane) - 1ull;
-        const uint32_t rp = op + (uint32_t)__popcll(mp & lm), rd = od + (uint32_t)__popcll(md & lm);
-        for (uint32_t i = 0; i < F; i++)
-            if (inpool && s_rank[i] == rp) s_hit[i] = j;
-        if (dead && s_rank[F] == rd) s_hit[F] = j;
-        base_pool += tp;
-        base_dead += td;
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) sel_seed_probe(d, o, L, scnt[o * 4 + 1], F, seed, round, seeds, n_seeds, s_hit, oo);
-}
-
-// Conflict-free phases for the round's exchanges e = o * (F + 2) + slot (initiator o, responder
-// out[e]; exchanges whose responder is down fail before any state change, as a refused
-// connection does, and are not scheduled).  Per phase p, IT rounds of a deterministic Luby
-// matching: an unscheduled exchange whose two endpoints are free in p takes p if its priority
-// key is the smallest at both endpoints.  busy = one bit per phase and node for 64 phases at a time (bit p mod 64;
-// the host clears it every 64 phases: a phase's bits are read only while it is being filled).  Up to
-// GS_MAX_SCHED_PHASES phases (round 6: the hubs of the reference's selection -- every node picks a seed while its
-// live set is empty -- need as many phases as their degree); exchanges left after the last are counted, not run.
-__device__ inline uint32_t fmix32(uint32_t h) {
-    h ^= h >> 16; h *= 0x85EBCA6Bu; h ^= h >> 13; h *= 0xC2B2AE35u; h ^= h >> 16;
-    return h;
-}
-__device__ inline bool luby_valid(const int32_t *out, const uint8_t *up, uint32_t e, uint32_t F, uint32_t &a,
-                                  uint32_t &b) {
-    const int32_t t = out[e];
-    if (t < 0 || !up[t]) return false;
-    a = e / (F + 2);
-    b = (uint32_t)t;
-    return true;
-}
-__device__ inline bool luby_active(const int32_t *out, const uint8_t *up, const uint32_t *eph,
-                                   const unsigned long long *busy, uint32_t e, uint32_t F, uint32_t p, uint32_t &a,
-                                   uint32_t &b) {
-    if (eph[e] != NONE) return false;
-    if (!luby_valid(out, up, e, F, a, b)) return false;
-    return !((busy[a] >> (p & 63u)) & 1ull) && !((busy[b] >> (p & 63u)) & 1ull);
-}
-__device__ inline unsigned long long luby_key(uint64_t seed, uint32_t round, uint32_t e, uint32_t p, uint32_t it) {
-    const uint32_t h = fmix32(e ^ fmix32((uint32_t)seed ^ fmix32(round * 0x9E3779B9u + p * 0x632BE5ABu + it)));
-    return ((unsigned long long)h << 32) | e;
-}
-__global__ __launch_bounds__(LB) void k_luby_min(const int32_t *out, const uint8_t *up, const uint32_t *eph,
-                                                 const unsigned long long *busy, unsigned long long *best, uint32_t E,
-                                                 uint32_t F, uint64_t seed, uint32_t round, uint32_t p, uint32_t it) {
-    const uint32_t e = blockIdx.x * LB + threadIdx.x;
-    uint32_t a, b;
-    if (e >= E || !luby_active(out, up, eph, busy, e, F, p, a, b)) return;
-    const unsigned long long k = luby_key(seed, round, e, p, it);
-    atomicMin(&best[a], k);
-    atomicMin(&best[b], k);
-}
-__global__ __launch_bounds__(LB) void k_luby_pick(const int32_t *out, const uint8_t *up, uint32_t *eph,
-                                                  unsigned long long *busy, const unsigned long long *best,
-                                                  unsigned long long *best_next, uint32_t E, uint32_t N, uint32_t F,
-                                                  uint64_t seed, uint32_t round, uint32_t p, uint32_t it,
-                                                  uint32_t *pcount) {
-    const uint32_t x = blockIdx.x * LB + threadIdx.x;
-    if (x < N) best_next[x] = ~0ull;
-    uint32_t a, b;
-    if (x >= E || !luby_active(out, up, eph, busy, x, F, p, a, b)) return;
-    const unsigned long long k = luby_key(seed, round, x, p, it);
-    if (best[a] == k && best[b] == k) {
-        eph[x] = p;
-        atomicOr(&busy[a], 1ull << (p & 63u));
-        atomicOr(&busy[b], 1ull << (p & 63u));
-        atomicAdd(&pcount[p], 1u);
-    }
-}
-// valid exchanges not scheduled yet
-__global__ __launch_bounds__(LB) void k_luby_left(const int32_t *out, const uint8_t *up, const uint32_t *eph,
-                                                  uint32_t E, uint32_t F, uint32_t *left) {
-    const uint32_t e = blockIdx.x * LB + threadIdx.x;
-    uint32_t a, b;
-    const bool l = e < E && eph[e] == NONE && luby_valid(out, up, e, F, a, b);
-    const unsigned long long m = __ballot(l);
-    if ((threadIdx.x & 63) == 0 && m) atomicAdd(left, (uint32_t)__popcll(m));
-}
-// scatter the scheduled exchanges into per-phase (initiator, responder) arrays: each workgroup ranks its
-// SCAT_PER x LB exchanges per phase in LDS and takes one range per phase with a single global atomic (a
-// returning atomic per exchange, or per wave and phase, serialises on the 16 or so phase counters: 0.59 ms).
-// Phases past the first 64 (hub exchanges only, a few per phase) take a global atomic each.
-constexpr uint32_t SCAT_PER = 4;
-__global__ __launch_bounds__(LB) void k_luby_scatter(const int32_t *out, const uint32_t *eph, uint32_t E, uint32_t F,
-                                                     const uint32_t *poff, uint32_t *pfill, int32_t *ini,
-                                                     int32_t *res) {
-    __shared__ uint32_t s_cnt[GS_MAX_PHASES], s_base[GS_MAX_PHASES];
-    if (threadIdx.x < GS_MAX_PHASES) s_cnt[threadIdx.x] = 0u;
-    __syncthreads();
-    uint32_t p[SCAT_PER], loc[SCAT_PER];
-#pragma unroll
-    for (uint32_t k = 0; k < SCAT_PER; k++) {
-        const uint32_t e = (blockIdx.x * SCAT_PER + k) * LB + threadIdx.x;
-        p[k] = e < E ? eph[e] : NONE;
-        loc[k] = p[k] < GS_MAX_PHASES ? atomicAdd(&s_cnt[p[k]], 1u) : 0u;
-    }
-    __syncthreads();
-    if (threadIdx.x < GS_MAX_PHASES && s_cnt[threadIdx.x])
-        s_base[threadIdx.x] = atomicAdd(&pfill[threadIdx.x], s_cnt[threadIdx.x]);
-    __syncthreads();
-#pragma unroll
-    for (uint32_t k = 0; k < SCAT_PER; k++) {
-        if (p[k] == NONE) continue;
-        const uint32_t e = (blockIdx.x * SCAT_PER + k) * LB + threadIdx.x;
-        const uint32_t slot = poff[p[k]] + (p[k] < GS_MAX_PHASES ? s_base[p[k]] + loc[k] : atomicAdd(&pfill[p[k]], 1u));
-        ini[slot] = (int32_t)(e / (F + 2));
-        res[slot] = out[e];
-    }
-}
-
-// ------------------------------------------------------------------ measurement kernels
-// Streaming copy: the measured HBM ceiling bench.py reports beside the 8 TB/s peak.  And read-only / write-only
-// streams at 4, 8 or 16 B per lane whose known byte counts calibrate rocprofv3's FETCH_SIZE / WRITE_SIZE.
-// measurement kernels (gs_stream_copy / _read / _write).  The copy: each wave moves contiguous 16 KiB chunks
-// (64 lanes x 16 B x 16 loads in flight per lane, non-temporal loads and stores), chunks dealt grid-stride
-// over 65,536 workgroups -- the fastest copy shape of tools/membench8.hip on the box (5.99 TB/s vs 5.30 for
-// round 3's grid-stride 8-deep copy, r4b)
-__global__ __launch_bounds__(256) void k_copy16(v4u_t *__restrict__ dst, const v4u_t *__restrict__ src, uint64_t n16) {
-    const uint64_t waves = (uint64_t)gridDim.x * 4u, wid = (uint64_t)blockIdx.x * 4u + (threadIdx.x >> 6);
-    const uint32_t lane = threadIdx.x & 63u;
-    const uint64_t chunks = n16 / 1024u;
-    for (uint64_t c = wid; c < chunks; c += waves) {
-        const uint64_t b = c * 1024u + lane;
-        v4u_t v[16];
-#pragma unroll
-        for (int u = 0; u < 16; u++) v[u] = __builtin_nontemporal_load(src + b + u * 64);
-#pragma unroll
-        for (int u = 0; u < 16; u++) __builtin_nontemporal_store(v[u], dst + b + u * 64);
-    }
-    // the tail (< 16 KiB): grid-stride
-    for (uint64_t i = chunks * 1024u + (uint64_t)blockIdx.x * 256u + threadIdx.x; i < n16; i += waves * 64u) dst[i] = src[i];
-}
-template <typename V>
-__global__ __launch_bounds__(256) void k_write(V *__restrict__ dst, uint64_t n) {
-    const uint64_t stride = (uint64_t)gridDim.x * 256u;
-    V v;
-    memset(&v, 0x5A, sizeof v);
-    for (uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x; i < n; i += stride) dst[i] = v;
-}
-__device__ __forceinline__ uint32_t fold(uint32_t v) { return v; }
-__device__ __forceinline__ uint32_t fold(uint2 v) { return v.x ^ v.y; }
-__device__ __forceinline__ uint32_t fold(uint4 v) { return v.x ^ v.y; }
-template <typename V>
-__global__ __launch_bounds__(256) void k_read(const V *__restrict__ src, uint64_t n, unsigned long long *sink) {
-    const uint64_t stride = (uint64_t)gridDim.x * 256u;
-    uint32_t acc = 0;
-    uint64_t i = (uint64_t)blockIdx.x * 256u + threadIdx.x;
-    for (; i + 3 * stride < n; i += 4 * stride) {
-        const V a = src[i], b = src[i + stride], c = src[i + 2 * stride], e = src[i + 3 * stride];
-        acc ^= fold(a) ^ fold(b) ^ fold(c) ^ fold(e);
-    }
-    for (; i < n; i += stride) acc ^= fold(src[i]);
-    if (acc == 0x9E3779B9u) atomicAdd(sink, 1ull);  // keeps the loads; practically never taken
-}
-
-// gs_mark: empty one-wave dispatches whose names bracket a region of a kernel trace (bench.py's timed rounds), so
-// tools/pmc_summary.py averages exactly the dispatches between them
-__global__ __launch_bounds__(WAVE) void k_mark_begin() {}
-__global__ __launch_bounds__(WAVE) void k_mark_end() {}
-
 }  // namespace
 
 // ====================================================================== C ABI
-struct gs_handle {
-    gs_config cfg;
-    Dev d;
-    uint32_t N, NP, K, KP, C, W;
-    uint32_t G, shard, col_lo, ncol;  // owner-column slice
-    bool sliced;                      // phases take the sliced path (G > 1, or GS_SLICED with one slice)
-    bool reports_pending;             // phases ran since the last gs_liveness
-    bool round_open;                  // gs_begin_round ran and gs_liveness has not closed the round yet
-    uint32_t last_phase_tick;
-    // sub-phases (Dev::v_round): the last phase's virtual tick (monotonic over the handle's life); a phase has run
-    // at last_phase_tick since the last round start / flush (a further phase at that tick is then a sub-phase);
-    // the plane base still needs its virtual base (set by the base's first phase)
-    uint32_t last_vt = 0;
-    bool sub_ok = false;
-    bool base_fresh = true;
-    uint64_t plane_flushes;           // mid-round report replays (rounds with phases > 16 ticks after the base)
-    uint64_t lag_sweeps = 0;          // k_hb_lag sweeps run (gs_counters.lag_sweeps)
-    uint32_t hb_incs;                 // rounds + phases since the last heartbeat-lag check (gs_check_heartbeat_lag)
-    uint32_t mv_incs = 0;             // GS_MV8: gs_owner_writes calls since the last lag check
-    uint32_t age_tick = 0;            // tick of the last window-age sweep (k_fd_age)
-    uint32_t max_tick = 0;            // latest tick of any operation (gs_latest_tick: decodes GS_R_FD_LAST)
-    void *reg[GS_NUM_REGIONS];
-    uint64_t bytes[GS_NUM_REGIONS];
-    hipStream_t stream;
-    uint32_t seq;
-    bool booted;
-    bool started = false;             // a round has begun (gs_set_ring_rows refuses from then on)
-    // canonical unsliced handles run a phase on candidate records (k_pass1 + k_settle); env GS_FUSED=1
-    // selects the single fused k_exchange (and, on sliced handles, the fused count pass) for A/B runs
-    bool split;
-    // record phases (env GS_PACK, A/B runs): 0 = k_pass1 with the speculative merge + k_settle (default),
-    // 1 = "fused": k_pass1 packing in the same workgroup, 2 = "split": k_pass1 + k_pack_slice
-    int pack_mode = 2;
-    bool age_init = false;            // age_tick holds the first operation's tick (fd_age)
-    // gs_set_timing: HIP events around each kernel launch of a kind (gs_ktimes), on the library's stream
-    bool timing;
-    uint32_t *heavy_buf = nullptr;  // k_pack_heavy's slot list (Dev::heavy): [0] = count, then up to N slot ids
-    uint16_t *sm_buf = nullptr;     // Dev::sm (one-slice prefix-view handles)
-    unsigned long long *vc_buf = nullptr;  // gs_view_census scratch: VC_NUM u64 accumulators, then the probes
-    std::vector<uint64_t> vc_img;          // ... and its host image (the upload before, the read after the pass)
-    unsigned long long *dc_buf = nullptr;  // gs_detect_census scratch: DC_NUM u64 accumulators
-    unsigned long long *ac_buf = nullptr;  // gs_age_census scratch: AC_NUM u64 accumulators, then the floor u32 [ncol]
-    unsigned long long *tc_buf = nullptr;  // gs_traffic_census scratch: NSHARD rows of TC_NUM u64 accumulators
-    hipStream_t hside = nullptr;    // k_pack_heavy's stream (forked after the lite slot work, joined after the packer)
-    hipEvent_t ev_fork = nullptr, ev_join = nullptr;
-    std::vector<std::pair<hipEvent_t, hipEvent_t>> tev[GS_KT_KINDS];
-    std::vector<hipEvent_t> evpool;
-    std::string err;
-    // sliced phases driven by the library (gs_comm_init: RCCL across processes; gs_run_phase_group:
-    // the slices of one process): device scratch for the gathered totals and chain states
-    ncclComm_t comm = nullptr;
-    struct {
-        uint64_t *tot = nullptr, *tot_all = nullptr, *chain = nullptr, *chainc = nullptr, *chain_all = nullptr;
-        uint64_t *pend = nullptr;  // device: the pending slots summed over the slices (sliced_phase's one read per step)
-        uint64_t *pin = nullptr, *pin_dev = nullptr;  // pinned host pair {pending, count} the kernel writes directly
-        uint32_t *list = nullptr;
-        uint32_t cap = 0;  // exchanges the buffers hold
-    } sc;
-    // gs_run_phase_group: each slice's kernels of a step run on a stream of its own (forked from and joined
-    // back into the group's stream around the step), so the slices' short launches overlap on the GPU
-    hipStream_t side = nullptr, home = nullptr;
-    hipEvent_t fj_fork = nullptr, fj_join = nullptr;
-    // gs_run_phase_group's batched launches: the group's GroupArgs in device memory and its host image as last
-    // uploaded (held by the group's first handle)
-    GroupArgs *grp = nullptr;
-    std::vector<uint8_t> grp_img;
-};
-
 namespace {
-
-int fail(gs_handle *h, int code, const char *fmt, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(buf, sizeof buf, fmt, ap);
-    va_end(ap);
-    if (h) h->err = buf;
-    return code;
-}
-
-#define HIPCHK(h, x)                                                                         \
-    do {                                                                                     \
-        hipError_t _e = (x);                                                                 \
-        if (_e != hipSuccess) return fail((h), GS_E_HIP, "%s: %s", #x, hipGetErrorString(_e)); \
-    } while (0)
-
-uint32_t round_up(uint32_t x, uint32_t m) { return (x + m - 1) / m * m; }
 
 // gs_set_timing: an event pair around each timed launch, recorded on the library's stream
 int time_begin(gs_handle *h, hipEvent_t &e0) {
@@ -7634,60 +5769,6 @@ int run_phase(gs_handle *h, const int32_t *ini, const int32_t *res, const uint8_
 }  // namespace
 }
 
-int gs_draw_cuts(gs_handle *h, const int32_t *ini, const int32_t *res, uint32_t n, uint64_t seed, uint32_t round,
-                 uint32_t phase, uint32_t loss_q32, uint8_t *legs) {
-    if (!h || (n && (!ini || !res || !legs))) return GS_E_INVALID;
-    if (!n) return GS_OK;
-    k_draw_cuts<<<(n + LB - 1) / LB, LB, 0, h->stream>>>(ini, res, n, seed, round, phase, loss_q32, legs);
-    HIPCHK(h, hipGetLastError());
-    return GS_OK;
-}
-
-extern "C++" {
-namespace {
-// the checks gs_draw_cuts_zoned and gs_filter_targets_zoned share, and the matrix as a kernel argument
-int zone_args(gs_handle *h, const char *fn, const uint8_t *zone, const uint32_t *link, uint32_t Z, ZoneLinks &lk) {
-    if (!zone) return fail(h, GS_E_INVALID, "%s: zone is NULL", fn);
-    if (!link) return fail(h, GS_E_INVALID, "%s: link is NULL", fn);
-    if (Z < 1 || Z > GS_MAX_ZONES) return fail(h, GS_E_INVALID, "%s: %u zones (1..%u)", fn, Z, GS_MAX_ZONES);
-    if (h->sliced || h->G > 1 || h->comm)
-        return fail(h, GS_E_UNSUPPORTED, "%s: zoned links run on one-slice handles only, as cut exchanges do", fn);
-    memset(&lk, 0, sizeof lk);
-    memcpy(lk.q, link, (size_t)Z * Z * 4);
-    return GS_OK;
-}
-}  // namespace
-}
-
-int gs_draw_cuts_zoned(gs_handle *h, const int32_t *ini, const int32_t *res, uint32_t n, uint64_t seed, uint32_t round,
-                       uint32_t phase, const uint8_t *zone, const uint32_t *link, uint32_t Z, uint8_t *legs) {
-    if (!h) return GS_E_INVALID;
-    if (!ini || !res) return fail(h, GS_E_INVALID, "gs_draw_cuts_zoned: initiators or responders is NULL");
-    if (!legs) return fail(h, GS_E_INVALID, "gs_draw_cuts_zoned: legs is NULL");
-    ZoneLinks lk;
-    if (const int rc = zone_args(h, "gs_draw_cuts_zoned", zone, link, Z, lk)) return rc;
-    if (!n) return GS_OK;
-    k_draw_cuts_zoned<<<(n + LB - 1) / LB, LB, 0, h->stream>>>(ini, res, n, h->N, seed, round, phase, zone, lk, Z, legs);
-    HIPCHK(h, hipGetLastError());
-    return GS_OK;
-}
-
-int gs_filter_targets_zoned(gs_handle *h, const int32_t *targets_in, int32_t *targets_out, uint32_t n_targets,
-                            const uint8_t *zone, const uint32_t *link, uint32_t Z, uint32_t *dropped) {
-    if (!h) return GS_E_INVALID;
-    if (!targets_in || !targets_out)
-        return fail(h, GS_E_INVALID, "gs_filter_targets_zoned: targets_in or targets_out is NULL");
-    ZoneLinks lk;
-    if (const int rc = zone_args(h, "gs_filter_targets_zoned", zone, link, Z, lk)) return rc;
-    if (!n_targets || n_targets % h->N)
-        return fail(h, GS_E_INVALID, "gs_filter_targets_zoned: %u targets are not a whole number of slots for each of "
-                    "%u nodes", n_targets, h->N);
-    k_zone_filter<<<(n_targets + LB - 1) / LB, LB, 0, h->stream>>>(targets_in, targets_out, n_targets, n_targets / h->N,
-                                                                  h->N, zone, lk, Z, dropped);
-    HIPCHK(h, hipGetLastError());
-    return GS_OK;
-}
-
 int gs_shard_columns(const gs_handle *h, uint32_t *col_lo, uint32_t *n_cols) {
     if (!h || !col_lo || !n_cols) return GS_E_INVALID;
     *col_lo = h->col_lo;
@@ -8443,95 +6524,6 @@ int gs_set_events(gs_handle *h, uint32_t *records, uint32_t capacity, uint32_t *
     return GS_OK;
 }
 
-int gs_select_peers(gs_handle *h, const uint8_t *up, uint32_t fanout, const int32_t *seeds, uint32_t n_seeds,
-                    uint64_t seed, uint32_t round, int32_t *targets, void *scratch) {
-    if (!h || !h->booted || !up || !targets || !scratch || fanout < 1 || fanout > 8 || (n_seeds && !seeds))
-        return GS_E_INVALID;
-    if (h->G > 1) return fail(h, GS_E_UNSUPPORTED, "gs_select_peers needs the whole matrix (one slice)");
-    uint32_t *scnt = (uint32_t *)scratch;
-    uint32_t *sel = scnt + (size_t)h->N * 4;
-    const bool canon = (h->cfg.flags & GS_CANONICAL) != 0;
-    if (canon && h->ncol <= SEL_ROW_IT * LB * 16u && !getenv("GS_SEL_SPLIT")) {  // one read of each row
-        k_sel_row16<<<h->N, LB, 0, h->stream>>>(h->d, up, fanout, seed, round, seeds, n_seeds, scnt, targets);
-        HIPCHK(h, hipGetLastError());
-        return GS_OK;
-    }
-    if (canon) k_sel_count16<<<h->N, LB, 0, h->stream>>>(h->d, up, scnt);
-    else k_sel_count<<<h->N, LB, 0, h->stream>>>(h->d, up, scnt);
-    HIPCHK(h, hipGetLastError());
-    k_sel_pick<<<(h->N + LB - 1) / LB, LB, 0, h->stream>>>(h->d, up, scnt, fanout, seed, round, sel);
-    HIPCHK(h, hipGetLastError());
-    if (canon) k_sel_resolve16<<<h->N, LB, 0, h->stream>>>(h->d, up, scnt, fanout, seed, round, seeds, n_seeds, sel, targets);
-    else k_sel_resolve<<<h->N, LB, 0, h->stream>>>(h->d, up, scnt, fanout, seed, round, seeds, n_seeds, sel, targets);
-    HIPCHK(h, hipGetLastError());
-    return GS_OK;
-}
-
-int gs_schedule_phases(gs_handle *h, const uint8_t *up, uint32_t fanout, const int32_t *targets, uint64_t seed,
-                       uint32_t round, uint32_t iters, uint32_t max_phases, void *scratch, int32_t *initiators,
-                       int32_t *responders, uint32_t *phase_offsets, uint32_t *unscheduled) {
-    if (!h || !up || !targets || !scratch || !initiators || !responders || !phase_offsets || !unscheduled ||
-        fanout < 1 || fanout > 8 || iters < 1 || max_phases < 1 || max_phases > GS_MAX_SCHED_PHASES)
-        return GS_E_INVALID;
-    const uint32_t N = h->N, E = N * (fanout + 2);
-    // scratch (GS_SCHED_SCRATCH_BYTES): eph[E] | pcount[P] | pfill[P] | poff[P] | left[4] | busy[N] (u64) |
-    // best[2][N] (u64)
-    const uint32_t P = max_phases;
-    uint32_t *eph = (uint32_t *)scratch;
-    uint32_t *pcount = eph + E;
-    uint32_t *pfill = pcount + P;
-    uint32_t *poff = pfill + P;
-    uint32_t *left = poff + P;
-    unsigned long long *busy = (unsigned long long *)(((uintptr_t)(left + 4) + 15) & ~(uintptr_t)15);
-    unsigned long long *best = busy + N;
-    hipStream_t s = h->stream;
-    HIPCHK(h, hipMemsetAsync(eph, 0xFF, (size_t)E * 4, s));
-    HIPCHK(h, hipMemsetAsync(pcount, 0, ((size_t)3 * P + 4) * 4, s));
-    HIPCHK(h, hipMemsetAsync(busy, 0, (size_t)N * 8, s));
-    HIPCHK(h, hipMemsetAsync(best, 0xFF, (size_t)N * 16, s));
-    const uint32_t gE = (std::max(E, N) + LB - 1) / LB;
-    // the two minimum buffers alternate by the GLOBAL iteration index, so each pick resets exactly
-    // the buffer the next iteration (of this phase or the next) reduces into, whatever iters is
-    uint32_t g = 0, nleft = 0;
-    // phases in blocks: 16 first (a round's schedule needs about 15-17 at fanout 3), then 4 at a time (the last few
-    // exchanges), each block followed by one count of the exchanges still without a phase
-    for (uint32_t p0 = 0, p1; p0 < max_phases; p0 = p1) {
-        p1 = std::min(max_phases, p0 + (p0 ? 4u : 16u));
-        // busy holds bit p mod 64: a block starting a new window of 64 phases starts from clear bits (blocks are
-        // 16 then 4 phases, so windows start at block boundaries)
-        if (p0 && (p0 & 63u) == 0) HIPCHK(h, hipMemsetAsync(busy, 0, (size_t)N * 8, s));
-        for (uint32_t p = p0; p < p1; p++)
-            for (uint32_t it = 0; it < iters; it++, g++) {
-                unsigned long long *b0 = best + (size_t)(g & 1) * N, *b1 = best + (size_t)((g + 1) & 1) * N;
-                k_luby_min<<<(E + LB - 1) / LB, LB, 0, s>>>(targets, up, eph, busy, b0, E, fanout, seed, round, p,
-                                                            it);
-                k_luby_pick<<<gE, LB, 0, s>>>(targets, up, eph, busy, b0, b1, E, N, fanout, seed, round, p, it,
-                                              pcount);
-            }
-        // stop once every valid exchange has a phase
-        HIPCHK(h, hipMemsetAsync(left, 0, 4, s));
-        k_luby_left<<<(E + LB - 1) / LB, LB, 0, s>>>(targets, up, eph, E, fanout, left);
-        HIPCHK(h, hipGetLastError());
-        HIPCHK(h, hipMemcpyAsync(&nleft, left, 4, hipMemcpyDeviceToHost, s));
-        HIPCHK(h, hipStreamSynchronize(s));
-        if (!nleft) break;
-    }
-    std::vector<uint32_t> cnt(max_phases);
-    HIPCHK(h, hipMemcpyAsync(cnt.data(), pcount, (size_t)max_phases * 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(h, hipStreamSynchronize(s));
-    std::vector<uint32_t> off(max_phases + 1);
-    off[0] = 0;
-    for (uint32_t p = 0; p < max_phases; p++) off[p + 1] = off[p] + cnt[p];
-    HIPCHK(h, hipMemcpyAsync(poff, off.data(), max_phases * 4, hipMemcpyHostToDevice, s));
-    k_luby_scatter<<<(E + SCAT_PER * LB - 1) / (SCAT_PER * LB), LB, 0, s>>>(targets, eph, E, fanout, poff, pfill,
-                                                                        initiators, responders);
-    HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipStreamSynchronize(s));
-    memcpy(phase_offsets, off.data(), (max_phases + 1) * 4);
-    *unscheduled = nleft;
-    return GS_OK;
-}
-
 int gs_fd_census(gs_handle *h, const uint8_t *up, gs_census *out) {
     if (!h || !h->booted || !up || !out) return GS_E_INVALID;
     k_zero_slots<<<1, NSHARD * 8, 0, h->stream>>>(h->d, C_CEN0, 5);
@@ -8550,272 +6542,6 @@ int gs_fd_census(gs_handle *h, const uint8_t *up, gs_census *out) {
     out->up_live = acc[2];
     out->down_pairs = acc[3];
     out->down_live = acc[4];
-    return GS_OK;
-}
-
-static_assert(sizeof(gs_view_totals) == 56 * 8, "gs_view_totals layout");
-static_assert(sizeof(gs_probe) == 8, "gs_probe layout");
-
-int gs_view_census(gs_handle *h, const uint8_t *up, uint32_t flags, const gs_probe *probes, uint32_t n_probes,
-                   uint64_t *reach, uint32_t *owners, uint32_t *rows, gs_view_totals *out) {
-    if (!h) return GS_E_INVALID;
-    if (!out) return fail(h, GS_E_INVALID, "gs_view_census: out is NULL");
-    if (flags & ~GS_VC_HEARTBEATS) return fail(h, GS_E_INVALID, "gs_view_census: unknown flags 0x%x", flags);
-    if (n_probes > GS_VC_MAX_PROBES) return fail(h, GS_E_INVALID, "gs_view_census: %u probes (at most %u)", n_probes, GS_VC_MAX_PROBES);
-    if (n_probes && (!probes || !reach)) return fail(h, GS_E_INVALID, "gs_view_census: probes without their arrays");
-    for (uint32_t i = 0; i < n_probes; i++)
-        if (probes[i].owner >= h->N) return fail(h, GS_E_INVALID, "gs_view_census: probe %u owner %u >= %u nodes", i, probes[i].owner, h->N);
-    if (!h->booted) return fail(h, GS_E_INVALID, "gs_view_census: not booted");
-    constexpr size_t WORDS = VC_NUM + GS_VC_MAX_PROBES;  // u64 accumulators, then {column, version} per probe
-    if (!h->vc_buf) HIPCHK(h, hipMalloc(&h->vc_buf, WORDS * 8));
-    h->vc_img.assign(WORDS, 0ull);
-    for (uint32_t i = 0; i < n_probes; i++) {
-        const uint32_t j = probes[i].owner;  // a probe of another slice's owner reaches nobody here
-        const uint32_t c = j >= h->col_lo && j - h->col_lo < h->ncol ? j - h->col_lo : NONE;
-        h->vc_img[VC_NUM + i] = (uint64_t)c | (uint64_t)probes[i].version << 32;
-    }
-    hipStream_t s = h->stream;
-    HIPCHK(h, hipMemcpyAsync(h->vc_buf, h->vc_img.data(), WORDS * 8, hipMemcpyHostToDevice, s));
-    if (owners) HIPCHK(h, hipMemsetAsync(owners, 0, (size_t)3 * h->ncol * 4, s));
-    if (rows) HIPCHK(h, hipMemsetAsync(rows, 0, (size_t)h->N * 4, s));
-    VcArgs a;
-    a.up = up;
-    a.flags = flags;
-    a.n_probes = n_probes;
-    a.acc = h->vc_buf;
-    a.probes = reinterpret_cast<const uint32_t *>(h->vc_buf + VC_NUM);
-    a.owners = owners;
-    a.rows = rows;
-    const Dev &d = h->d;
-    const bool swar = (d.flags & GS_CANONICAL) && d.hb8 && d.mv8 && d.self_pk;
-    const uint32_t per = swar ? 16u : 8u, chunks = (h->ncol + LB * per - 1) / (LB * per);
-    const uint32_t grid = (h->N + VC_BAND - 1) / VC_BAND * chunks;
-    if (swar)
-        k_view_census<true><<<grid, LB, 0, s>>>(d, a, chunks);
-    else
-        k_view_census<false><<<grid, LB, 0, s>>>(d, a, chunks);
-    HIPCHK(h, hipGetLastError());
-    HIPCHK(h, hipMemcpyAsync(h->vc_img.data(), h->vc_buf, (size_t)VC_NUM * 8, hipMemcpyDeviceToHost, s));
-    HIPCHK(h, hipStreamSynchronize(s));
-    const uint64_t *acc = h->vc_img.data();
-    memset(out, 0, sizeof *out);
-    out->observers = acc[VC_OBS];
-    out->views = acc[VC_VIEWS];
-    out->unknown = acc[VC_UNK];
-    out->behind = acc[VC_BEHIND];
-    out->inexact = acc[VC_INEX];
-    out->max_version_lag = acc[VC_MAXV];
-    out->max_heartbeat_lag = acc[VC_MAXH];
-    // the kernel counts the non-zero lags: bucket 0 is the rest of the known views
-    uint64_t nzv = 0, nzh = 0;
-    for (uint32_t b = 1; b < GS_VC_BUCKETS; b++) {
-        nzv += out->version_lag_hist[b] = acc[VC_VH + b];
-        nzh += out->heartbeat_lag_hist[b] = acc[VC_HH + b];
-    }
-    out->version_lag_hist[0] = out->views - nzv;
-    if (flags & GS_VC_HEARTBEATS) out->heartbeat_lag_hist[0] = out->views - nzh;
-    for (uint32_t i = 0; i < n_probes; i++) reach[i] = acc[VC_REACH + i];
-    return GS_OK;
-}
-
-static_assert(sizeof(gs_detect_totals) == 120 * 8, "gs_detect_totals layout");
-
-extern "C++" {
-namespace {
-// gs_detect_census (obs == up) and gs_detect_census_for: `fn` names the entry point in gs_last_error
-int detect_census(gs_handle *h, const char *fn, const uint8_t *obs, const uint8_t *up, const uint32_t *down_since,
-                  uint32_t tick, const double *thresholds, uint32_t n_thresholds, uint32_t *targets, uint32_t *rows,
-                  gs_detect_totals *out) {
-    if (!h) return GS_E_INVALID;
-    if (!obs) return fail(h, GS_E_INVALID, "%s: observers is NULL", fn);
-    if (!up) return fail(h, GS_E_INVALID, "%s: up is NULL", fn);
-    if (!out) return fail(h, GS_E_INVALID, "%s: out is NULL", fn);
-    if (n_thresholds > GS_DC_MAX_THRESHOLDS)
-        return fail(h, GS_E_INVALID, "%s: %u thresholds (at most %u)", fn, n_thresholds, GS_DC_MAX_THRESHOLDS);
-    if (n_thresholds && !thresholds) return fail(h, GS_E_INVALID, "%s: thresholds is NULL", fn);
-    // gs_create's bound on phi_threshold, for every swept threshold: a window silent for >= 2^15 ticks is above it
-    const double widest = std::max((double)h->cfg.max_interval_ticks, h->cfg.prior_weighted / 5.0 * 64.0);
-    double tmin = 0.0, tmax = 0.0;
-    for (uint32_t i = 0; i < n_thresholds; i++) {
-        const double x = thresholds[i];
-        if (!(x >= 0.0) || !(x * widest < (double)FD_OLD_AGE))
-            return fail(h, GS_E_INVALID, "%s: threshold %u = %g is NaN, negative or too large "
-                        "(threshold x max(max_interval, prior) must stay below 2^15 ticks)", fn, i, x);
-        tmin = i ? std::min(tmin, x) : x;
-        tmax = i ? std::max(tmax, x) : x;
-    }
-    if ((int32_t)(tick - h->max_tick) < 0 || tick - h->max_tick >= FD_OLD_AGE)
-        return fail(h, GS_E_INVALID, "%s: tick %u is before the handle's latest tick %u, or 2^15 or more "
-                    "past it", fn, tick, h->max_tick);
-    if (!h->booted) return fail(h, GS_E_INVALID, "%s: not booted", fn);
-    if (!h->dc_buf) HIPCHK(h, hipMalloc(&h->dc_buf, (size_t)DC_NUM * 8));
-    hipStream_t s = h->stream;
-    HIPCHK(h, hipMemsetAsync(h->dc_buf, 0, (size_t)DC_NUM * 8, s));
-    if (targets) {
-        HIPCHK(h, hipMemsetAsync(targets, 0, (size_t)4 * h->ncol * 4, s));
-        HIPCHK(h, hipMemsetAsync(targets + (size_t)2 * h->ncol, 0xFF, (size_t)h->ncol * 4, s));
-    }
-    if (rows) HIPCHK(h, hipMemsetAsync(rows, 0, (size_t)2 * h->N * 4, s));
-    DcArgs a;
-    a.obs = obs;
-    a.up = up;
-    a.down_since = down_since;
-    a.tick = tick;
-    a.tdec = h->max_tick;
-    a.n_thr = n_thresholds;
-    // binary32 phi carries a relative error below 2^-20: 2^-10 clear of every threshold decides all of them
-    a.lo_all = (float)(tmin * (1.0 - 0x1p-10));
-    a.hi_all = (float)(tmax * (1.0 + 0x1p-10));
-    for (uint32_t i = 0; i < GS_DC_MAX_THRESHOLDS; i++) a.thr[i] = i < n_thresholds ? thresholds[i] : 0.0;
-    a.acc = h->dc_buf;
-    a.targets = targets;
-    a.rows = rows;
-    const uint32_t chunks = (h->ncol + LB * 16 - 1) / (LB * 16);
-    const uint32_t grid = (h->N + DC_BAND - 1) / DC_BAND * chunks;
-    if (n_thresholds)
-        k_detect_census<true><<<grid, LB, 0, s>>>(h->d, a, chunks);
-    else
-        k_detect_census<false><<<grid, LB, 0, s>>>(h->d, a, chunks);
-    HIPCHK(h, hipGetLastError());
-    if (targets) {
-        k_detect_fix<<<(h->ncol + LB - 1) / LB, LB, 0, s>>>(targets, h->ncol);
-        HIPCHK(h, hipGetLastError());
-    }
-    uint64_t acc[DC_NUM];
-    HIPCHK(h, hipMemcpyAsync(acc, h->dc_buf, sizeof acc, hipMemcpyDeviceToHost, s));
-    HIPCHK(h, hipStreamSynchronize(s));
-    memset(out, 0, sizeof *out);
-    out->observers = acc[DC_OBS];
-    out->up_pairs = acc[DC_UP_PAIRS];
-    out->up_live = acc[DC_UP_LIVE];
-    out->up_dead = acc[DC_UP_DEAD];
-    out->up_unknown = out->up_pairs - out->up_live - out->up_dead;
-    out->down_pairs = acc[DC_DN_PAIRS];
-    out->down_live = acc[DC_DN_LIVE];
-    out->down_dead = acc[DC_DN_DEAD];
-    out->down_unknown = out->down_pairs - out->down_live - out->down_dead;
-    out->up_windows = acc[DC_UP_WIN];
-    out->down_windows = acc[DC_DN_WIN];
-    out->up_phi = acc[DC_UP_PHI];
-    out->down_phi = acc[DC_DN_PHI];
-    out->old_windows = acc[DC_OLD];
-    out->early_deaths = acc[DC_EARLY];
-    out->max_detect_latency = acc[DC_MAX];
-    out->max_undetected_age = acc[DC_MAX + 1];
-    out->max_false_age = acc[DC_MAX + 2];
-    for (uint32_t b = 0; b < GS_DC_BUCKETS; b++) {
-        out->detect_latency_hist[b] = acc[DC_HIST + b];
-        out->undetected_age_hist[b] = acc[DC_HIST + GS_DC_BUCKETS + b];
-        out->false_age_hist[b] = acc[DC_HIST + 2 * GS_DC_BUCKETS + b];
-    }
-    for (uint32_t i = 0; i < n_thresholds; i++) {
-        out->up_over[i] = acc[DC_OVER + i];
-        out->down_over[i] = acc[DC_OVER + GS_DC_MAX_THRESHOLDS + i];
-    }
-    return GS_OK;
-}
-}  // namespace
-}
-
-int gs_detect_census(gs_handle *h, const uint8_t *up, const uint32_t *down_since, uint32_t tick, const double *thresholds,
-                     uint32_t n_thresholds, uint32_t *targets, uint32_t *rows, gs_detect_totals *out) {
-    if (h && !up) return fail(h, GS_E_INVALID, "gs_detect_census: up is NULL");
-    return detect_census(h, "gs_detect_census", up, up, down_since, tick, thresholds, n_thresholds, targets, rows, out);
-}
-
-int gs_detect_census_for(gs_handle *h, const uint8_t *observers, const uint8_t *up, const uint32_t *down_since,
-                         uint32_t tick, const double *thresholds, uint32_t n_thresholds, uint32_t *targets, uint32_t *rows,
-                         gs_detect_totals *out) {
-    return detect_census(h, "gs_detect_census_for", observers, up, down_since, tick, thresholds, n_thresholds, targets,
-                         rows, out);
-}
-
-static_assert(sizeof(gs_age_totals) == 80 * 8, "gs_age_totals layout");
-
-int gs_write_log_words(const gs_handle *h, uint32_t *wl) {
-    if (!h || !wl) return GS_E_INVALID;
-    *wl = round_up(h->K * (h->C - 1) + 1, 4);  // GS_R_VLOG's row: versions 1 .. K (C - 1)
-    return GS_OK;
-}
-
-int gs_write_log_init(gs_handle *h, uint32_t *wlog) {
-    if (!h) return GS_E_INVALID;
-    if (!wlog) return fail(h, GS_E_INVALID, "gs_write_log_init: wlog is NULL");
-    uint32_t WL = 0;
-    gs_write_log_words(h, &WL);
-    HIPCHK(h, hipMemsetAsync(wlog, 0xFF, (size_t)h->ncol * WL * 4, h->stream));
-    return GS_OK;
-}
-
-int gs_note_writes(gs_handle *h, uint32_t tick, uint32_t *wlog) {
-    if (!h) return GS_E_INVALID;
-    if (!wlog) return fail(h, GS_E_INVALID, "gs_note_writes: wlog is NULL");
-    if (!h->booted) return fail(h, GS_E_INVALID, "gs_note_writes: not booted");
-    uint32_t WL = 0;
-    gs_write_log_words(h, &WL);
-    k_note_writes<<<(h->ncol + LB - 1) / LB, LB, 0, h->stream>>>(h->d, wlog, WL, tick);
-    HIPCHK(h, hipGetLastError());
-    return GS_OK;
-}
-
-int gs_age_census(gs_handle *h, const uint8_t *up, const uint32_t *wlog, uint32_t tick, uint32_t flags, uint32_t *floor,
-                  uint32_t *rows, uint32_t *done, gs_age_totals *out) {
-    if (!h) return GS_E_INVALID;
-    if (!wlog) return fail(h, GS_E_INVALID, "gs_age_census: wlog is NULL");
-    if (!out) return fail(h, GS_E_INVALID, "gs_age_census: out is NULL");
-    if (flags) return fail(h, GS_E_INVALID, "gs_age_census: unknown flags 0x%x", flags);
-    if ((int32_t)(tick - h->max_tick) < 0 || tick - h->max_tick >= FD_OLD_AGE)
-        return fail(h, GS_E_INVALID, "gs_age_census: tick %u is before the handle's latest tick %u, or 2^15 or more "
-                    "past it", tick, h->max_tick);
-    if (!h->booted) return fail(h, GS_E_INVALID, "gs_age_census: not booted");
-    const size_t bytes = (size_t)AC_NUM * 8 + (size_t)h->ncol * 4;
-    if (!h->ac_buf) HIPCHK(h, hipMalloc(&h->ac_buf, bytes));
-    hipStream_t s = h->stream;
-    AcArgs a;
-    a.up = up;
-    a.wlog = wlog;
-    gs_write_log_words(h, &a.WL);
-    a.tick = tick;
-    a.acc = h->ac_buf;
-    a.floor = reinterpret_cast<uint32_t *>(h->ac_buf + AC_NUM);
-    a.rows = rows;
-    a.done = done;
-    const Dev &d = h->d;
-    HIPCHK(h, hipMemsetAsync(h->ac_buf, 0, (size_t)AC_NUM * 8, s));
-    // a column's floor starts at the owner's own max_version: the value with no counted observer, or none behind
-    HIPCHK(h, hipMemcpyAsync(a.floor, d.self_mv, (size_t)h->ncol * 4, hipMemcpyDeviceToDevice, s));
-    if (rows) HIPCHK(h, hipMemsetAsync(rows, 0, (size_t)h->N * 4, s));
-    const bool swar = (d.flags & GS_CANONICAL) && d.mv8;
-    const uint32_t per = swar ? 16u : 8u, chunks = (h->ncol + LB * per - 1) / (LB * per);
-    const uint32_t grid = (h->N + VC_BAND - 1) / VC_BAND * chunks;
-    if (swar)
-        k_age_census<true><<<grid, LB, 0, s>>>(d, a, chunks);
-    else
-        k_age_census<false><<<grid, LB, 0, s>>>(d, a, chunks);
-    HIPCHK(h, hipGetLastError());
-    k_age_owners<<<(h->ncol + LB - 1) / LB, LB, 0, s>>>(d, a);
-    HIPCHK(h, hipGetLastError());
-    if (floor) HIPCHK(h, hipMemcpyAsync(floor, a.floor, (size_t)h->ncol * 4, hipMemcpyDeviceToDevice, s));
-    uint64_t acc[AC_NUM];
-    HIPCHK(h, hipMemcpyAsync(acc, h->ac_buf, sizeof acc, hipMemcpyDeviceToHost, s));
-    HIPCHK(h, hipStreamSynchronize(s));
-    memset(out, 0, sizeof *out);
-    out->observers = acc[AC_OBS];
-    out->pairs = out->observers * h->ncol;
-    out->unknown = acc[AC_UNK];
-    out->behind = acc[AC_BEHIND];
-    out->unlogged = acc[AC_UNLOG];
-    out->max_age = acc[AC_MAXAGE];
-    out->spread_writes = acc[AC_SPREAD];
-    out->pending_writes = acc[AC_PENDING];
-    out->unlogged_writes = acc[AC_UNLOG_W];
-    out->max_spread_latency = acc[AC_MAXSPREAD];
-    out->max_pending_age = acc[AC_MAXPEND];
-    for (uint32_t b = 0; b < GS_AC_BUCKETS; b++) {
-        out->age_hist[b] = acc[AC_AH + b];
-        out->spread_hist[b] = acc[AC_SH + b];
-        out->pending_age_hist[b] = acc[AC_PH + b];
-    }
     return GS_OK;
 }
 
@@ -8887,48 +6613,6 @@ int gs_traffic_census(gs_handle *h, const int32_t *ini, const int32_t *res, cons
             else w[c] += v;
         }
     return GS_OK;
-}
-
-int gs_stream_copy(void *dst, const void *src, uint64_t bytes, void *stream) {
-    if (!dst || !src || (bytes & 15u) || ((uintptr_t)dst & 15u) || ((uintptr_t)src & 15u)) return GS_E_INVALID;
-    k_copy16<<<65536, 256, 0, (hipStream_t)stream>>>((v4u_t *)dst, (const v4u_t *)src, bytes / 16);
-    return hipGetLastError() == hipSuccess ? GS_OK : GS_E_HIP;
-}
-
-int gs_stream_write(void *dst, uint64_t bytes, uint32_t width, void *stream) {
-    if (!dst || (width != 4 && width != 8 && width != 16) || (bytes % width) || ((uintptr_t)dst & 15u))
-        return GS_E_INVALID;
-    if (width == 4)
-        k_write<uint32_t><<<32768, 256, 0, (hipStream_t)stream>>>((uint32_t *)dst, bytes / 4);
-    else if (width == 8)
-        k_write<uint2><<<32768, 256, 0, (hipStream_t)stream>>>((uint2 *)dst, bytes / 8);
-    else
-        k_write<uint4><<<32768, 256, 0, (hipStream_t)stream>>>((uint4 *)dst, bytes / 16);
-    return hipGetLastError() == hipSuccess ? GS_OK : GS_E_HIP;
-}
-
-int gs_stream_read(const void *src, uint64_t bytes, uint32_t width, uint64_t *sink, void *stream) {
-    if (!src || !sink || (width != 4 && width != 8 && width != 16) || (bytes % width) || ((uintptr_t)src & 15u))
-        return GS_E_INVALID;
-    if (width == 4)
-        k_read<uint32_t><<<32768, 256, 0, (hipStream_t)stream>>>((const uint32_t *)src, bytes / 4,
-                                                                 (unsigned long long *)sink);
-    else if (width == 8)
-        k_read<uint2><<<32768, 256, 0, (hipStream_t)stream>>>((const uint2 *)src, bytes / 8,
-                                                              (unsigned long long *)sink);
-    else
-        k_read<uint4><<<32768, 256, 0, (hipStream_t)stream>>>((const uint4 *)src, bytes / 16,
-                                                              (unsigned long long *)sink);
-    return hipGetLastError() == hipSuccess ? GS_OK : GS_E_HIP;
-}
-
-int gs_mark(uint32_t which, void *stream) {
-    if (which > 1) return GS_E_INVALID;
-    if (which == 0)
-        k_mark_begin<<<1, WAVE, 0, (hipStream_t)stream>>>();
-    else
-        k_mark_end<<<1, WAVE, 0, (hipStream_t)stream>>>();
-    return hipGetLastError() == hipSuccess ? GS_OK : GS_E_HIP;
 }
 
 int gs_sync(gs_handle *h) {

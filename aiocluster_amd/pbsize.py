@@ -8,7 +8,7 @@ The only ``optional`` field, ``NodeDeltaPb.max_version`` (``messages.proto:65``)
 is always set by the reference (``state.py:389``), so it is always present.
 
 These functions are the host-side definition; the device computes the same
-quantities in ``aiocluster_amd/csrc/gossip_kernels.hip`` (``pb_*`` helpers).
+quantities in ``aiocluster_amd/csrc/gossip_sim.hip`` (``vlen``, ``ufield``, ``sfield``, ``msgf``).
 They are pinned against the reference's own ``ByteSize()`` by
 ``tests/golden/pbsize.json`` (see ``oracle/gen_golden.py``).
 """

@@ -338,15 +338,66 @@ class ShardGroup:
         parts = [s.fd_census(up) for s in self.slices]
         local = {k: sum(p[k] for p in parts) for k in parts[0]}
         if isinstance(self.comm, DistComm):
-            import torch
-
             from ._lib import CENSUS_FIELDS
 
-            dev = "cpu" if self.comm.dist.get_backend(self.comm.group) == "gloo" else "cuda"
-            v = torch.tensor([local[k] for k in CENSUS_FIELDS], dtype=torch.int64, device=dev)
-            self.comm.dist.all_reduce(v, group=self.comm.group)
-            local = dict(zip(CENSUS_FIELDS, (int(x) for x in v.tolist())))
+            local = dict(zip(CENSUS_FIELDS, self._all_reduce([local[k] for k in CENSUS_FIELDS], "cuda")))
         return local
+
+    def _all_reduce(self, vals: list, dev, maxima: bool = False) -> list:
+        """``vals`` (ints) summed, or maxed, over the ranks of a ``DistComm``: one all-reduce."""
+        import torch
+
+        d = self.comm.dist
+        v = torch.tensor(vals, dtype=torch.int64, device="cpu" if d.get_backend(self.comm.group) == "gloo" else dev)
+        d.all_reduce(v, op=d.ReduceOp.MAX if maxima else d.ReduceOp.SUM, group=self.comm.group)
+        return [int(x) for x in v.tolist()]
+
+    def _merge_census(self, parts: list, totals, maxima, lists) -> dict:
+        """The slices' census dicts ``parts`` as one: the fields ``totals`` summed, those of them in ``maxima`` maxed
+        and ``observers`` taken once (every slice counts the same rows), then the list-valued fields ``lists`` summed
+        element by element.  Over a ``DistComm`` one SUM and one MAX all-reduce, as ``fd_census`` does."""
+        sums = [k for k in totals if k not in maxima and k != "observers"]
+        vec = [sum(p[k] for p in parts) for k in sums]
+        for k in lists:
+            vec += [sum(p[k][b] for p in parts) for b in range(len(parts[0][k]))]
+        mx = [max(p[k] for p in parts) for k in maxima]
+        if isinstance(self.comm, DistComm):
+            dev = self.slices[0].device
+            vec, mx = self._all_reduce(vec, dev), self._all_reduce(mx, dev, maxima=True)
+        out = {"observers": parts[0]["observers"]}
+        it = iter(vec)
+        out.update((k, next(it)) for k in sums)
+        out.update(zip(maxima, mx))
+        out = {k: out[k] for k in totals}
+        for k in lists:
+            out[k] = [next(it) for _ in parts[0][k]]
+        return out
+
+    def _join_owners(self, parts: list):
+        """The slices' per-owner tensors joined along the owner axis; over a ``DistComm`` gathered through the comm,
+        padded to the widest slice (the last one is shorter), so every rank gets the whole axis."""
+        import torch
+
+        t = torch.cat(parts)
+        if isinstance(self.comm, DistComm):
+            blk = _slice_block(self.n, self.comm.world)
+            pad = torch.zeros(blk, dtype=t.dtype, device=t.device)
+            pad[: t.numel()] = t
+            allp = self.comm.gather([pad])
+            t = torch.cat([allp[g, : min(blk, self.n - g * blk)] for g in range(self.comm.world)])
+        return t
+
+    def _reduce_rows(self, parts: list, maxima: bool = False):
+        """The slices' per-row tensors summed (int32), or maxed, over the slices and the ranks of a ``DistComm``."""
+        import torch
+
+        def red(t):
+            return t.amax(0) if maxima else t.sum(0, dtype=torch.int32)
+
+        t = red(torch.stack(parts))
+        if isinstance(self.comm, DistComm):
+            t = red(self.comm.gather([t]))
+        return t
 
     def view_census(self, up=None, heartbeats: bool = False, probes=(), per_owner: bool = False,
                     per_row: bool = False) -> dict:
@@ -354,52 +405,19 @@ class ShardGroup:
         over the slices (``observers`` taken once), maxima maxed, the per-owner tensors joined along the owner
         axis.  Over a ``DistComm`` the sums and maxima are all-reduced as ``fd_census`` does and the per-owner
         parts gathered through the comm (every rank gets the whole result)."""
-        import torch
-
         from ._lib import VIEW_HIST_FIELDS, VIEW_MAX_FIELDS, VIEW_TOTAL_FIELDS
 
         probes = list(probes)
         parts = [s.view_census(up, heartbeats, probes, per_owner, per_row) for s in self.slices]
-        sums = [k for k in VIEW_TOTAL_FIELDS if k not in VIEW_MAX_FIELDS and k != "observers"]
-        vec = [sum(p[k] for p in parts) for k in sums]
-        for k in VIEW_HIST_FIELDS:
-            vec += [sum(p[k][b] for p in parts) for b in range(len(parts[0][k]))]
-        vec += [sum(p["reach"][i] for p in parts) for i in range(len(probes))]
-        mx = [max(p[k] for p in parts) for k in VIEW_MAX_FIELDS]
-        dist = isinstance(self.comm, DistComm)
-        dev = self.slices[0].device
-        if dist:
-            d = self.comm.dist
-            cdev = "cpu" if d.get_backend(self.comm.group) == "gloo" else dev
-            v = torch.tensor(vec, dtype=torch.int64, device=cdev)
-            m = torch.tensor(mx, dtype=torch.int64, device=cdev)
-            d.all_reduce(v, group=self.comm.group)
-            d.all_reduce(m, op=d.ReduceOp.MAX, group=self.comm.group)
-            vec, mx = [int(x) for x in v.tolist()], [int(x) for x in m.tolist()]
-        out = {"observers": parts[0]["observers"]}
-        it = iter(vec)
-        out.update((k, next(it)) for k in sums)
-        out.update(zip(VIEW_MAX_FIELDS, mx))
-        out = {k: out[k] for k in VIEW_TOTAL_FIELDS}
-        for k in VIEW_HIST_FIELDS:
-            out[k] = [next(it) for _ in parts[0][k]]
+        out = self._merge_census(parts, VIEW_TOTAL_FIELDS, VIEW_MAX_FIELDS, VIEW_HIST_FIELDS + ["reach"])
+        reach = out.pop("reach")
         out["converged"] = out["behind"] == 0 and out["unknown"] == 0
-        out["reach"] = [next(it) for _ in probes]
+        out["reach"] = reach
         if per_owner:
             for k in ("owner_behind", "owner_unknown", "owner_max_lag"):
-                t = torch.cat([p[k] for p in parts])
-                if dist:  # slices differ in width (the last one is shorter): gathered padded to the widest
-                    blk = _slice_block(self.n, self.comm.world)
-                    pad = torch.zeros(blk, dtype=t.dtype, device=t.device)
-                    pad[: t.numel()] = t
-                    allp = self.comm.gather([pad])
-                    t = torch.cat([allp[g, : min(blk, self.n - g * blk)] for g in range(self.comm.world)])
-                out[k] = t
+                out[k] = self._join_owners([p[k] for p in parts])
         if per_row:
-            t = torch.stack([p["row_stale"] for p in parts]).sum(0, dtype=torch.int32)
-            if dist:
-                t = self.comm.gather([t]).sum(0, dtype=torch.int32)
-            out["row_stale"] = t
+            out["row_stale"] = self._reduce_rows([p["row_stale"] for p in parts])
         return out
 
     def age_census(self, up=None, tick: int | None = None, per_owner: bool = False, per_row: bool = False,
@@ -409,47 +427,14 @@ class ShardGroup:
         maxima maxed -- ``row_max_age`` too, a row's largest age over all columns --, ``owner_floor`` joined along the
         owner axis.  Over a ``DistComm`` the sums and maxima are all-reduced and the parts gathered, as
         ``view_census`` does."""
-        import torch
-
         from ._lib import AGE_HIST_FIELDS, AGE_MAX_FIELDS, AGE_TOTAL_FIELDS
 
         parts = [s.age_census(up, tick, per_owner, per_row, spread) for s in self.slices]
-        sums = [k for k in AGE_TOTAL_FIELDS if k not in AGE_MAX_FIELDS and k != "observers"]
-        vec = [sum(p[k] for p in parts) for k in sums]
-        for k in AGE_HIST_FIELDS:
-            vec += [sum(p[k][b] for p in parts) for b in range(len(parts[0][k]))]
-        mx = [max(p[k] for p in parts) for k in AGE_MAX_FIELDS]
-        dist = isinstance(self.comm, DistComm)
-        dev = self.slices[0].device
-        if dist:
-            d = self.comm.dist
-            cdev = "cpu" if d.get_backend(self.comm.group) == "gloo" else dev
-            v = torch.tensor(vec, dtype=torch.int64, device=cdev)
-            m = torch.tensor(mx, dtype=torch.int64, device=cdev)
-            d.all_reduce(v, group=self.comm.group)
-            d.all_reduce(m, op=d.ReduceOp.MAX, group=self.comm.group)
-            vec, mx = [int(x) for x in v.tolist()], [int(x) for x in m.tolist()]
-        out = {"observers": parts[0]["observers"]}
-        it = iter(vec)
-        out.update((k, next(it)) for k in sums)
-        out.update(zip(AGE_MAX_FIELDS, mx))
-        out = {k: out[k] for k in AGE_TOTAL_FIELDS}
-        for k in AGE_HIST_FIELDS:
-            out[k] = [next(it) for _ in parts[0][k]]
+        out = self._merge_census(parts, AGE_TOTAL_FIELDS, AGE_MAX_FIELDS, AGE_HIST_FIELDS)
         if per_owner:
-            t = torch.cat([p["owner_floor"] for p in parts])
-            if dist:  # slices differ in width (the last one is shorter): gathered padded to the widest
-                blk = _slice_block(self.n, self.comm.world)
-                pad = torch.zeros(blk, dtype=t.dtype, device=t.device)
-                pad[: t.numel()] = t
-                allp = self.comm.gather([pad])
-                t = torch.cat([allp[g, : min(blk, self.n - g * blk)] for g in range(self.comm.world)])
-            out["owner_floor"] = t
+            out["owner_floor"] = self._join_owners([p["owner_floor"] for p in parts])
         if per_row:
-            t = torch.stack([p["row_max_age"] for p in parts]).amax(0)
-            if dist:
-                t = self.comm.gather([t]).amax(0)
-            out["row_max_age"] = t
+            out["row_max_age"] = self._reduce_rows([p["row_max_age"] for p in parts], maxima=True)
         return out
 
     def detect_census(self, up, tick: int | None = None, down_since=None, thresholds=(), per_target: bool = False,
@@ -460,54 +445,20 @@ class ShardGroup:
         need no combining).  Over a ``DistComm`` the sums and maxima are all-reduced and the per-target parts
         gathered, as ``view_census`` does.  ``observers``: as for ``GossipSim.detect_census`` (the rows counted,
         apart from the targets' truth ``up``)."""
-        import torch
-
         from ._lib import DETECT_HIST_FIELDS, DETECT_MAX_FIELDS, DETECT_OVER_FIELDS, DETECT_TOTAL_FIELDS
         from .detect import detect_rates
 
         thresholds = list(thresholds)
         parts = [s.detect_census(up, tick, down_since, thresholds, per_target, per_row, observers=observers)
                  for s in self.slices]
-        sums = [k for k in DETECT_TOTAL_FIELDS if k not in DETECT_MAX_FIELDS and k != "observers"]
-        lists = DETECT_HIST_FIELDS + DETECT_OVER_FIELDS
-        vec = [sum(p[k] for p in parts) for k in sums]
-        for k in lists:
-            vec += [sum(p[k][b] for p in parts) for b in range(len(parts[0][k]))]
-        mx = [max(p[k] for p in parts) for k in DETECT_MAX_FIELDS]
-        dist = isinstance(self.comm, DistComm)
-        dev = self.slices[0].device
-        if dist:
-            d = self.comm.dist
-            cdev = "cpu" if d.get_backend(self.comm.group) == "gloo" else dev
-            v = torch.tensor(vec, dtype=torch.int64, device=cdev)
-            m = torch.tensor(mx, dtype=torch.int64, device=cdev)
-            d.all_reduce(v, group=self.comm.group)
-            d.all_reduce(m, op=d.ReduceOp.MAX, group=self.comm.group)
-            vec, mx = [int(x) for x in v.tolist()], [int(x) for x in m.tolist()]
-        out = {"observers": parts[0]["observers"]}
-        it = iter(vec)
-        out.update((k, next(it)) for k in sums)
-        out.update(zip(DETECT_MAX_FIELDS, mx))
-        out = {k: out[k] for k in DETECT_TOTAL_FIELDS}
-        for k in lists:
-            out[k] = [next(it) for _ in parts[0][k]]
+        out = self._merge_census(parts, DETECT_TOTAL_FIELDS, DETECT_MAX_FIELDS, DETECT_HIST_FIELDS + DETECT_OVER_FIELDS)
         out.update(detect_rates(out))
         if per_target:
             for k in ("target_live_by", "target_dead_by", "target_first_tod", "target_last_tod"):
-                t = torch.cat([p[k] for p in parts])
-                if dist:  # slices differ in width (the last one is shorter): gathered padded to the widest
-                    blk = _slice_block(self.n, self.comm.world)
-                    pad = torch.zeros(blk, dtype=t.dtype, device=t.device)
-                    pad[: t.numel()] = t
-                    allp = self.comm.gather([pad])
-                    t = torch.cat([allp[g, : min(blk, self.n - g * blk)] for g in range(self.comm.world)])
-                out[k] = t
+                out[k] = self._join_owners([p[k] for p in parts])
         if per_row:
             for k in ("row_false_suspicions", "row_undetected"):
-                t = torch.stack([p[k] for p in parts]).sum(0, dtype=torch.int32)
-                if dist:
-                    t = self.comm.gather([t]).sum(0, dtype=torch.int32)
-                out[k] = t
+                out[k] = self._reduce_rows([p[k] for p in parts])
         return out
 
     def export(self) -> dict:

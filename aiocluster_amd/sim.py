@@ -67,7 +67,7 @@ FD_WIN, FD_OLD, FD_OLD_AGE = 4, 8, 1 << 15
 
 
 def unpack_fd(st8, last16, sc, tick: int, sum_bits: int):
-    """Host restatement of the device's fd_get (gossip_sim.hip): see GossipSim.unpack_fd."""
+    """Host restatement of the device's fd_get (csrc/gossip_common.h): see GossipSim.unpack_fd."""
     st8 = np.asarray(st8).view(np.uint8).astype(np.uint32)
     l16 = np.asarray(last16).view(np.uint16).astype(np.int64)
     sc = np.asarray(sc).view(np.uint32)

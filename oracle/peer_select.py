@@ -1,5 +1,5 @@
 """CPU restatement of the device peer selection and phase schedule (gs_select_peers /
-gs_schedule_phases in aiocluster_amd/csrc/gossip_sim.hip).
+gs_schedule_phases in aiocluster_amd/csrc/gossip_select.hip).
 
 TEST INFRASTRUCTURE: the checker for the HIP path; only tests/ import it.
 

@@ -1,4 +1,4 @@
-"""The word tricks of k_sel_row16 (aiocluster_amd/csrc/gossip_sim.hip), restated in numpy and checked
+"""The word tricks of k_sel_row16 (aiocluster_amd/csrc/gossip_select.hip), restated in numpy and checked
 exhaustively against the per-column rules they replace (k_sel_resolve16's loop: live = membership 1,
 dead = membership bit 1, a column counts only inside the row and off the observer's own column).
 

@@ -5,6 +5,7 @@
 set -e
 R=$(cd "$(dirname "$0")/.." && pwd)
 OUT=${OUT:-libgossip_sim_kw4.so}
+C=$R/aiocluster_amd/csrc
 hipcc --offload-arch=gfx950 -O3 -ffp-contract=off -std=c++17 -fPIC -shared -DGS_KW4_ONLY \
-  -o $R/aiocluster_amd/lib/$OUT $R/aiocluster_amd/csrc/gossip_sim.hip -L/opt/rocm/lib -lrccl \
-  -Wl,-rpath,/opt/rocm/lib "$@"
+  -o $R/aiocluster_amd/lib/$OUT $C/gossip_sim.hip $C/gossip_census.hip $C/gossip_select.hip $C/gossip_probe.hip \
+  -L/opt/rocm/lib -lrccl -Wl,-rpath,/opt/rocm/lib "$@"
